@@ -1,8 +1,17 @@
 """Headline benchmark: pCN steps/s on Lorenz-96 d=40, 2000 RK4 steps, 65 536 chains.
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload cfg3|cfg4|cfg5]
+  python bench.py [--gpus N --steps K --warmup W] [--workload cfg3|cfg4|cfg5] [--full] [--dump-outputs DIR]
   (N > 1: started once, it launches torch.distributed.run with N ranks itself;
    under an external torch.distributed.run WORLD_SIZE must equal N)
+
+A plain run does what value needs and nothing else: set-up, W untimed steps,
+the clock settle, the K timed steps of the end-to-end leg, the line.  --full
+adds every other leg described below (the kernel leg and the roofline on it,
+the host-buffer run, the paired accept streams, the other precision and
+arithmetic, the mixing posterior, configs 4 and 5, the CPU baseline), each of
+which --no-cpu / --no-extra / --no-configs / --no-parity still drops.
+--dump-outputs DIR writes what the timed run returned to its caller as
+DIR/<name>.npy (dump_outputs).
 
 A "step" is one pCN step of every chain of the ensemble: propose, run the
 forward map (cfg3: 2000 RK4 steps of Lorenz-96, d=40), evaluate Φ, accept or
@@ -521,6 +530,37 @@ def cpu_baseline(prob, dtype_np, budget_s=15.0):
                       f"({'f64' if dtype_np == np.float64 else 'f32'}), C oracle, {threads} threads, {el:.1f} s"}
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(path, res, n_total):
+    """What the timed run_sharded call returned to its caller, as path/<name>.npy
+    (float64): phi and accepts of every chain of the node and the posterior
+    mean, and this rank's per-chain rows u, sum_u, sum_u2 (gather='mean' leaves
+    them on their rank; with one GPU they are every chain's).  Rows of the
+    per-chain arrays are kept whole up to DUMP_BYTES in all; a larger result is
+    cut to a sample of chains that depends on the shapes alone (seed 0, sorted,
+    the same chains in every array), their positions in chain_rows.npy (into
+    the rank's rows) and chain_ids.npy (global ids, into phi and accepts)."""
+    os.makedirs(path, exist_ok=True)
+    host = lambda a: (a.detach().double().cpu().numpy() if isinstance(a, torch.Tensor)  # noqa: E731
+                      else np.asarray(a, dtype=np.float64))
+    lo, hi = res["chain_range"]
+    local = {k: host(res[k]).reshape(hi - lo, -1) for k in ("u", "sum_u", "sum_u2")}
+    per_chain = {k: host(res[k]).reshape(n_total) for k in ("phi", "accepts")}
+    row_bytes = 8 * (sum(a.shape[1] for a in local.values()) + len(per_chain) + 2)
+    rows = np.arange(hi - lo)
+    if (hi - lo) * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(hi - lo, size=DUMP_BYTES // row_bytes, replace=False))
+    out = {k: a[rows] for k, a in local.items()}
+    out.update({k: a[lo + rows] for k, a in per_chain.items()})
+    out["chain_rows"], out["chain_ids"] = rows.astype(np.float64), (lo + rows).astype(np.float64)
+    out["mean"] = host(res["mean"])
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(out)
+
+
 def _free_port():
     sk = socket.socket()
     sk.bind(("127.0.0.1", 0))
@@ -575,6 +615,13 @@ def main():
     ap.add_argument("--spec-width", type=int, default=0, help="speculative slots per chain (0 = auto, 1 = off)")
     ap.add_argument("--settle", type=float, default=0.3,
                     help="seconds of untimed G evaluations before the warm-up steps (clock ramp; 0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside value's: the kernel leg and its roofline, the host-buffer (PCIe) run, paired "
+                         "accept streams, f32 and REFERENCE arith, the mixing posterior, configs 4 and 5 and the CPU "
+                         "baseline (a plain run times value only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed run returned (u, phi, accepts, sum_u, sum_u2, "
+                         "mean) as DIR/<name>.npy, float64, at most 60 MB (a fixed sample of chains beyond that)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the short cfg4 / cfg5 runs in extra.configs")
@@ -597,6 +644,11 @@ def main():
         raise SystemExit("--share-device needs --dist-backend gloo (RCCL wants one GPU per rank)")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and args.kernel_only:
+        raise SystemExit("--dump-outputs writes the end-to-end run's result; --kernel-only has none")
+    if not args.full:  # a plain run: value's leg only
+        args.no_cpu = args.no_extra = args.no_configs = args.no_parity = True
+    kernel_leg = args.full or args.kernel_only
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
@@ -630,16 +682,19 @@ def main():
     tdt = torch.float64 if args.dtype == "f64" else torch.float32
     ndt = np.float64 if args.dtype == "f64" else np.float32
 
-    # 1. kernel leg: device-resident sweeps, HIP events (the roofline's kernel time)
+    # 1. kernel leg (--full): device-resident sweeps, HIP events (the roofline's kernel time)
     # (a launch never exceeds the timed steps: the plan reported is the one timed)
+    # a plain run builds its chains too, untimed: the end-to-end leg settles the clocks on them
     per_launch = min(args.steps_per_launch or auto_per_launch(per_rank), max(1, steps))
     w = Workload(prob, per_rank, lo_rank, tdt, dev, args.lanes, per_launch=per_launch,
                  spec_width=args.spec_width)
-    log(f"kernel leg: {steps} pCN steps ({args.dtype}, {per_rank} chains/GPU, {per_launch} steps/launch, "
-        f"lanes={w.lanes}, spec_width={w.spec_width})")
-    el_k, kern_ms = timed(w, steps, warmup, world, args.settle)
-    kernel_rate = total_chains * steps / el_k
-    log(f"kernel leg: {el_k:.3f} s, kernel {kern_ms:.3f} ms/launch, {kernel_rate / 1e6:.2f} M steps/s")
+    el_k = kern_ms = kernel_rate = None
+    if kernel_leg:
+        log(f"kernel leg: {steps} pCN steps ({args.dtype}, {per_rank} chains/GPU, {per_launch} steps/launch, "
+            f"lanes={w.lanes}, spec_width={w.spec_width})")
+        el_k, kern_ms = timed(w, steps, warmup, world, args.settle)
+        kernel_rate = total_chains * steps / el_k
+        log(f"kernel leg: {el_k:.3f} s, kernel {kern_ms:.3f} ms/launch, {kernel_rate / 1e6:.2f} M steps/s")
     lanes_k, cpl_k, spec_k = w.lanes, w.chains_per_lane, w.spec_width
     # the end-to-end legs settle the clocks on the kernel leg's chains (their
     # swept state, untouched: ipmc_potential into a scratch Φ)
@@ -661,8 +716,11 @@ def main():
         e2e, res = timed_run(prob, ndt, dev, total_chains, steps, warmup, world, gather=gather_mode, settle=settle)
     value = e2e["pcn_steps_per_s"]
     log(f"end-to-end: {e2e['wall_s']:.3f} s, {value / 1e6:.2f} M steps/s")
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, res, total_chains)
+        log(f"--dump-outputs: {', '.join(names)} in {args.dump_outputs}")
     e2e_pcie = None
-    if not args.kernel_only:
+    if args.full and not args.kernel_only:
         # the same run handing over host buffers (u_0 in, states and sums out):
         # the PCIe-inclusive rate, never value
         e2e_pcie = timed_run(prob, ndt, dev, total_chains, steps, warmup, world, gather=gather_mode, settle=settle,
@@ -680,10 +738,12 @@ def main():
     accept_rate = e2e["accept_rate"]
     del res
 
-    extra = {"kernel_pcn_steps_per_s": kernel_rate, "kernel_ms": kern_ms,
-             "kernel_note": "device-resident state, raw ipmc_pcn_sweep launches of steps_per_launch steps, HIP "
-                            "events on the launch stream (the roofline's kernel time); no H2D / D2H / gather",
-             "run_e2e_moments": e2e, "run_e2e_pcie": e2e_pcie}
+    extra = {"run_e2e_moments": e2e}
+    if kernel_leg:
+        extra = {"kernel_pcn_steps_per_s": kernel_rate, "kernel_ms": kern_ms,
+                 "kernel_note": "device-resident state, raw ipmc_pcn_sweep launches of steps_per_launch steps, HIP "
+                                "events on the launch stream (the roofline's kernel time); no H2D / D2H / gather",
+                 "run_e2e_moments": e2e, "run_e2e_pcie": e2e_pcie}
     parity = {}
     if not args.no_parity and world == 1 and not args.kernel_only:
         # north_star's bit-exact accept streams, for the arithmetic value is
@@ -763,7 +823,7 @@ def main():
     del settle, w
 
     flop = per_rank * per_launch * prob.flop
-    achieved = flop / (kern_ms * 1e-3) / 1e12
+    achieved = flop / (kern_ms * 1e-3) / 1e12 if kernel_leg else None
     peak = PEAK_TFLOPS[args.dtype]
     is_l96_40 = args.workload == "cfg3"
     pmc, pmc_src = pmc_record(args.dtype, per_rank, lanes_k) if (per_launch == 1 and is_l96_40) else (None, None)
@@ -793,6 +853,7 @@ def main():
             "ms_per_step": e2e["ms_per_step"],
             "higher_is_better": True,
             "kernel_only": bool(args.kernel_only),
+            "full": bool(args.full),
             "scaling": args.scaling,
             "vs_baseline": None,
             "dtype": args.dtype,
@@ -824,7 +885,7 @@ def main():
                 "clock_settle": "untimed G evaluations of the kernel leg's chains before the kernel leg's and before "
                                 "each end-to-end leg's timed region (after its warm-up run)",
             },
-            "roofline": {
+            "roofline": None if not kernel_leg else {
                 "bound": "valu",
                 "achieved": achieved,
                 "peak": peak,

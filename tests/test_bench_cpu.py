@@ -25,6 +25,47 @@ def test_help_lists_the_options():
         assert opt in r.stdout, opt
 
 
+def test_help_lists_full_and_dump_outputs():
+    r = _bench("--help")
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
+def test_dump_outputs_has_nothing_to_write_for_kernel_only():
+    r = _bench("--kernel-only", "--dump-outputs", "unused")
+    assert r.returncode != 0 and "--kernel-only has none" in r.stderr
+
+
+def test_dump_outputs_samples_a_large_result(tmp_path):
+    """A result beyond the budget is cut to the same sorted sample of chains in
+    every per-chain array, whatever the values; a small one is written whole."""
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    n, k, lo = 4096, 8, 1024  # this rank's rows [1024, 3072) of 4096 chains
+    rng = np.random.default_rng(1)
+    res = {"chain_range": (lo, lo + 2048), "phi": rng.normal(size=n), "accepts": np.arange(n, dtype=np.int64),
+           "mean": rng.normal(size=k), "u": rng.normal(size=(2048, k)), "sum_u": rng.normal(size=(2048, k)),
+           "sum_u2": rng.normal(size=(2048, k))}
+    names = bench.dump_outputs(str(tmp_path / "whole"), res, n)
+    got = {f: np.load(tmp_path / "whole" / f"{f}.npy") for f in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["u"], res["u"]) and np.array_equal(got["phi"], res["phi"][lo:lo + 2048])
+    assert np.array_equal(got["chain_ids"], np.arange(lo, lo + 2048)) and np.array_equal(got["mean"], res["mean"])
+    budget, bench.DUMP_BYTES = bench.DUMP_BYTES, 100 * 8 * (3 * k + 4)
+    try:
+        bench.dump_outputs(str(tmp_path / "cut"), res, n)
+    finally:
+        bench.DUMP_BYTES = budget
+    cut = {f: np.load(tmp_path / "cut" / f"{f}.npy") for f in names}
+    rows = cut["chain_rows"].astype(int)
+    assert len(rows) == 100 and (np.diff(rows) > 0).all() and rows.max() < 2048
+    assert np.array_equal(cut["sum_u2"], res["sum_u2"][rows]) and np.array_equal(cut["accepts"], lo + rows)
+    size = sum((tmp_path / "cut" / f"{f}.npy").stat().st_size for f in names)
+    assert size <= 100 * 8 * (3 * k + 4) + 8 * k + 128 * len(names)  # the budget, the mean and the .npy headers
+
+
 def test_unknown_workload_is_refused():
     r = _bench("--workload", "cfg9")
     assert r.returncode != 0 and "invalid choice" in r.stderr

@@ -31,7 +31,8 @@ def _free_port():
 def test_bench_two_ranks_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--chains", "4096", "--scaling", "weak", "--no-cpu", "--no-extra",
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--chains", "4096", "--scaling", "weak", "--full", "--no-cpu",
+           "--no-extra",
            "--no-configs", "--dist-backend", "gloo", "--share-device"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -47,7 +48,7 @@ def test_bench_two_ranks_rehearsal():
 
 def test_bench_gpus_2_launches_its_own_ranks():
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-cpu", "--dist-backend", "gloo", "--share-device"]
+           "--full", "--no-cpu", "--dist-backend", "gloo", "--share-device"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -83,7 +84,7 @@ def test_bench_cfg5_workload_two_ranks():
     """`bench.py --gpus 2 --workload cfg5`: one line for BASELINE config 5 at its
     full ensemble (2^20 chains, 524 288 per rank)."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--workload", "cfg5", "--steps", "2",
-           "--warmup", "1", "--no-cpu", "--dist-backend", "gloo", "--share-device"]
+           "--warmup", "1", "--full", "--no-cpu", "--dist-backend", "gloo", "--share-device"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -102,8 +103,8 @@ def test_bench_one_rank_over_rccl():
     8-GPU line issues, on hardware (RCCL refuses two ranks on one GPU)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--chains", "8192", "--no-cpu", "--no-extra",
-           "--no-configs", "--no-parity"]
+           "--gpus", "1", "--steps", "3", "--warmup", "1", "--chains", "8192", "--full", "--no-cpu",
+           "--no-extra", "--no-configs", "--no-parity"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,4 +1,4 @@
-"""Summarise a rocprofv3 kernel trace of `bench.py --steps K --warmup W
+"""Summarise a rocprofv3 kernel trace of `bench.py --full --steps K --warmup W
 --no-extra ...` (tools/sessions/r5.sh e2etrace): the settle loop's G
 evaluations, the kernel leg's one-step sweeps and each run_sharded call of the
 end-to-end leg (warm-up run, then the timed run), with their per-step kernel

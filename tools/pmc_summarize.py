@@ -9,7 +9,7 @@ order) -- bench.py's kernel leg when the run also has later legs.
 Inputs: the three separate passes (FETCH_SIZE; WRITE_SIZE; SQ_WAVES,
 SQ_INSTS_VALU, SQ_WAVE_CYCLES, SQ_BUSY_CYCLES, GRBM_GUI_ACTIVE), each
 `rocprofv3 --pmc ... --kernel-trace --output-format csv` of
-`bench.py --steps 5 --warmup 1 --no-cpu --no-extra`.  HBM bytes per launch =
+`bench.py --full --steps 5 --warmup 1 --no-cpu --no-extra`.  HBM bytes per launch =
 2 x FETCH_SIZE + WRITE_SIZE (KB): on gfx950 FETCH_SIZE counts 128-B requests
 at 64 B (MI355X_MICROARCH.md, HBM / rocprofv3 section).  The algorithmic bytes
 are the compulsory per-chain traffic of one sweep: u read (d·s B), Φ and

@@ -1,7 +1,7 @@
 """The bench line's kernel time from a rocprofv3 kernel trace, restricted to
 the launches the line times.
 
-  rocprofv3 --kernel-trace --stats -d DIR -o bench -- python bench.py --steps K --warmup W ...
+  rocprofv3 --kernel-trace --stats -d DIR -o bench -- python bench.py --full --steps K --warmup W ...
   python tools/trace_summary.py DIR K W [bench_line.json] > summary.json
 
 bench.py's kernel leg runs first: W untimed and then K timed launches of the
