@@ -32,6 +32,10 @@
  *   len_burn_in                       burgers/utilities.py:134-167  ipmc_burn_in
  *   np.mean over the samples          sampler.py:20-28 callers ipmc_block_sums (the many-chain posterior
  *                                     (e.g. stuart_examples.py)  mean's fixed-order block sums, on the device)
+ *   (nothing: the reference runs one chain and has no cross-chain statistic)
+ *                                                             ipmc_split_stats, ipmc_mean_acov,
+ *                                                             ipmc_moments_stats, ipmc_centered_sq_block_sums
+ *                                                             (split-R-hat, ESS and MCSE over the ensemble)
  *
  * The reference has no FFI of its own (it is duck-typed Python); these entry
  * points are what a ctypes binding of its plugin API binds.
@@ -273,6 +277,42 @@ int ipmc_ordered_sum(const double* rows, int64_t n_rows, int64_t k, int64_t row_
    Blocks run in parallel.  Device pointers; out [ceil(n_rows / B), k]. */
 int ipmc_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride, int64_t block_rows,
                     double div, double* out, void* stream);
+
+/* Convergence across chains (diagnostics.convergence: split-R-hat, ESS, MCSE).  These replace nothing in
+   the reference, which runs one chain.  Additive to ABI 13.
+   Sample t of component v of chain c is x[c*stride_chain + t*stride_t + v*stride_var], t < len, 1 <= k <= 256,
+   dtype float or double (widened to double on load).  With N = len/2 (an odd last sample is dropped), split
+   chain m < 2*n_chains is samples [0, N) of chain m for m < n_chains and samples [N, 2N) of chain
+   m - n_chains otherwise.  No floating-point atomics; every sum has a fixed order that depends on the
+   arguments alone, so two calls give the same bits.  n_chains == 0 is a no-op; len < 4 is invalid.
+
+   ipmc_split_stats: mean_out[m, v] = mean of the split chain, var_out[m, v] = Σ (x - mean)² / (N - 1)
+   (two passes, centred); both double [2*n_chains, k]. */
+int ipmc_split_stats(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
+                     int64_t stride_t, int64_t stride_var, double* mean_out, double* var_out, void* stream);
+
+/* partial_out[b, tau, v] = Σ_m γ_m(tau) over the split chains m of block b (block_chains consecutive split
+   chains, the last block possibly shorter), added from zero in m order, for tau <= max_lag <= N - 1, where
+   γ_m(tau) = (1/N) Σ_{i < N - tau} (x_i - mean[m, v]) (x_{i+tau} - mean[m, v]) ascending in i (split chains of up
+   to 64 samples read in place, up to 8192 staged in LDS, longer ones tiled: the same operations in the same
+   order on each path).  mean: double [2*n_chains, k] from
+   ipmc_split_stats; partial_out: double [ceil(2*n_chains / block_chains), max_lag + 1, k].  Blocks are
+   independent; the per-chain lag sums are never stored. */
+int ipmc_mean_acov(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
+                   int64_t stride_t, int64_t stride_var, const double* mean, int32_t max_lag, int64_t block_chains,
+                   double* partial_out, void* stream);
+
+/* Per-chain mean and sample variance from the sums a keep="moments" run holds (ipmc_sweep.sum_u / sum_u2 over
+   n steps, double [n_chains, k]): mean_out = sum_u / n, var_out = (sum_u2 - sum_u*sum_u / n) / (n - 1), these
+   IEEE operations in this order.  The subtraction cancels: relative error about (mean/sd)² 2^-53.  n >= 2. */
+int ipmc_moments_stats(const double* sum_u, const double* sum_u2, int64_t n_chains, int32_t k, int64_t n,
+                       double* mean_out, double* var_out, void* stream);
+
+/* ipmc_block_sums over the centred squares: out[b][j] = (((0 + d_0²) + d_1²) + ...), d_r = rows[bB + r][j] -
+   center[j], over the rows of block b in row order -- the second pass of a variance across chains.
+   center: double [k]; out: double [ceil(n_rows / block_rows), k]. */
+int ipmc_centered_sq_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride,
+                                const double* center, int64_t block_rows, double* out, void* stream);
 
 /* Lorenz-96 layout of a ONE-step launch (no speculation) when lanes_per_chain = chains_per_lane = 0:
    returns lanes_per_chain, and chains_per_lane * 100 + lanes_per_chain from ipmc_auto_layout.

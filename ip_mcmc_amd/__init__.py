@@ -39,8 +39,12 @@ from .rng import PhiloxRNG, PhiloxStream
 # ConstSteppCNProposer under its older name)
 pCNProposer = ConstSteppCNProposer
 from ._lib import IpmcError, UnsupportedOnDevice
+from .diagnostics import convergence, moments_convergence, split_rhat
 
 __all__ = [
+    "convergence",
+    "split_rhat",
+    "moments_convergence",
     "MCMCSampler",
     "ProposerBase",
     "ConstSteppCNProposer",

@@ -499,3 +499,435 @@ extern "C" int ipmc_autocorr(const void* x, int32_t dtype, int64_t n_series, int
   }
   return check_launch("autocorr_kernel");
 }
+
+// ------------------------------------------------- convergence across chains
+// Split-R-hat / ESS / MCSE over an ensemble (diagnostics.convergence; these
+// replace nothing in the reference, which never has more than one chain).
+// Chain c's samples x[c, t, :], t < len, are cut into split chains m < 2C of
+// N = len / 2 samples: m < C is x[m, :N], m >= C is x[m - C, N:2N] (an odd
+// last sample is dropped).  Everything is widened to fp64 on load.
+//
+// Lane mappings of the per-series sums (split_stats), chosen from the shape
+// alone (cv_lanes_over_time), so the bits never depend on the grid:
+//   over components  one lane per (m, v), t ascending in the lane: adjacent
+//                    lanes read adjacent components (k = 40..256, short series);
+//   over time        one wave per (m, v), lane l sums t = l, l + 64, ... ascending,
+//                    then a fixed xor butterfly (32, 16, ..., 1): for k = 2..3
+//                    with many samples the waves of one block share the lines
+//                    they read, and with unit time stride the loads are dense.
+namespace ipmc {
+
+constexpr int kCvBlock = 256;
+// products formed per batch before they are added in order: a lone wave's
+// dependent add would otherwise wait out an LDS latency per term (measured:
+// ~120 cycles per term without it)
+constexpr int kCvBatch = 16;
+
+__host__ __device__ inline bool cv_lanes_over_time(int64_t N, int k, int64_t stride_t) {
+  return N >= 32 && (stride_t == 1 || k < 16);
+}
+
+template <typename T>
+__device__ inline const T* cv_series(const T* x, int64_t m, int64_t n_chains, int64_t N, int64_t s_chain,
+                                     int64_t s_t) {
+  return m < n_chains ? x + m * s_chain : x + (m - n_chains) * s_chain + N * s_t;
+}
+
+// every lane ends with the same bits (a + b == b + a)
+__device__ inline double cv_wave_sum(double v) {
+  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kCvBlock) void split_stats_vars_kernel(const T* __restrict__ x, int64_t n_chains,
+                                                                   int64_t N, int k, int64_t s_chain, int64_t s_t,
+                                                                   int64_t s_var, double* __restrict__ mean_out,
+                                                                   double* __restrict__ var_out) {
+  const int64_t g = (int64_t)blockIdx.x * kCvBlock + threadIdx.x;
+  if (g >= 2 * n_chains * k) return;
+  const int64_t m = g / k;
+  const int v = (int)(g - m * k);
+  const T* a = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
+  double s = 0.0;
+#pragma unroll 8
+  for (int64_t t = 0; t < N; ++t) s = s + (double)a[t * s_t];
+  const double mean = s / (double)N;
+  double q = 0.0;
+#pragma unroll 8
+  for (int64_t t = 0; t < N; ++t) {
+    const double d = (double)a[t * s_t] - mean;
+    q = q + d * d;
+  }
+  mean_out[g] = mean;
+  var_out[g] = q / (double)(N - 1);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kCvBlock) void split_stats_time_kernel(const T* __restrict__ x, int64_t n_chains,
+                                                                   int64_t N, int k, int64_t s_chain, int64_t s_t,
+                                                                   int64_t s_var, double* __restrict__ mean_out,
+                                                                   double* __restrict__ var_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t g = (int64_t)blockIdx.x * (kCvBlock / 64) + (threadIdx.x >> 6);  // one series per wave
+  if (g >= 2 * n_chains * k) return;
+  const int64_t m = g / k;
+  const int v = (int)(g - m * k);
+  const T* a = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
+  double s = 0.0;
+  for (int64_t t = lane; t < N; t += 64) s = s + (double)a[t * s_t];
+  const double mean = cv_wave_sum(s) / (double)N;
+  double q = 0.0;
+  for (int64_t t = lane; t < N; t += 64) {
+    const double d = (double)a[t * s_t] - mean;
+    q = q + d * d;
+  }
+  q = cv_wave_sum(q);
+  if (lane == 0) {
+    mean_out[g] = mean;
+    var_out[g] = q / (double)(N - 1);
+  }
+}
+
+// partial[b, tau, v] = sum over the split chains m of block b (block_chains
+// consecutive ones, from zero in m order) of gamma_m(tau) = r_m(tau) / N,
+// r_m(tau) = sum_i xs[i] xs[i + tau] ascending in i, xs = x - mean[m, v].
+// One workgroup per (b, v, tile of kCvBlock lags); a thread owns one lag and
+// keeps its running sum in a register while the block walks its split chains,
+// each series staged (centred) in LDS once: the (2C, k, L) per-chain lag sums
+// never exist.  The products are compute, not bandwidth (N loads feed N * L
+// multiply-adds), so the staging load's stride matters little here.
+template <typename T>
+__global__ __launch_bounds__(kCvBlock) void mean_acov_kernel(const T* __restrict__ x, int64_t n_chains, int64_t N,
+                                                            int k, int64_t s_chain, int64_t s_t, int64_t s_var,
+                                                            const double* __restrict__ mean, int max_lag,
+                                                            int64_t block_chains, double* __restrict__ partial) {
+  __shared__ double xs[kAcMaxLen];
+  const int64_t b = blockIdx.x / k;
+  const int v = (int)(blockIdx.x - b * k);
+  const int tau = (int)blockIdx.y * kCvBlock + (int)threadIdx.x;
+  const int64_t m0 = b * block_chains;
+  const int64_t m1 = (m0 + block_chains) < 2 * n_chains ? (m0 + block_chains) : 2 * n_chains;
+  const int n = (int)N;
+  double acc = 0.0;
+  for (int64_t m = m0; m < m1; ++m) {
+    const T* a = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
+    const double mu = mean[m * k + v];
+    for (int t = threadIdx.x; t < n; t += kCvBlock) xs[t] = (double)a[t * s_t] - mu;
+    __syncthreads();
+    if (tau <= max_lag) {
+      double r = 0.0;
+      int i = 0;
+      for (; i + kCvBatch + tau <= n; i += kCvBatch) {  // the reads of a batch in flight together
+        double p[kCvBatch];
+#pragma unroll
+        for (int u = 0; u < kCvBatch; ++u) p[u] = xs[i + u] * xs[i + u + tau];
+#pragma unroll
+        for (int u = 0; u < kCvBatch; ++u) r = r + p[u];  // added in ascending i all the same
+      }
+      for (; i + tau < n; ++i) r = r + xs[i] * xs[i + tau];
+      acc = acc + r / (double)N;
+    }
+    __syncthreads();
+  }
+  if (tau <= max_lag) partial[(b * ((int64_t)max_lag + 1) + tau) * k + v] = acc;
+}
+
+// N <= kCvDirectLen: staging a handful of samples costs a block two barriers
+// and a load latency per split chain with most of its lanes idle (N = 10 for
+// the 65 536 x 20 ensemble).  Here one lane owns (b, tau, v), v fastest, and
+// reads its two factors straight from global memory (adjacent lanes adjacent
+// components; a chain's few samples stay in the caches across its lags).  The
+// same centred factors in the same ascending order: the bits of mean_acov_kernel.
+constexpr int kCvDirectLen = 64;
+
+template <typename T>
+__global__ __launch_bounds__(kCvBlock) void mean_acov_direct_kernel(const T* __restrict__ x, int64_t n_chains,
+                                                                   int64_t N, int k, int64_t s_chain, int64_t s_t,
+                                                                   int64_t s_var, const double* __restrict__ mean,
+                                                                   int max_lag, int64_t block_chains,
+                                                                   int64_t n_blocks, double* __restrict__ partial) {
+  const int64_t g = (int64_t)blockIdx.x * kCvBlock + threadIdx.x;
+  const int64_t per_block = ((int64_t)max_lag + 1) * k;
+  if (g >= n_blocks * per_block) return;
+  const int64_t b = g / per_block;
+  const int64_t rest = g - b * per_block;
+  const int tau = (int)(rest / k);
+  const int v = (int)(rest - (int64_t)tau * k);
+  const int64_t m0 = b * block_chains;
+  const int64_t m1 = (m0 + block_chains) < 2 * n_chains ? (m0 + block_chains) : 2 * n_chains;
+  const int n = (int)N - tau;
+  double acc = 0.0;
+  for (int64_t m = m0; m < m1; ++m) {
+    const T* a = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
+    const double mu = mean[m * k + v];
+    double r = 0.0;
+#pragma unroll 4
+    for (int i = 0; i < n; ++i) r = r + ((double)a[i * s_t] - mu) * ((double)a[(i + tau) * s_t] - mu);
+    acc = acc + r / (double)N;
+  }
+  partial[g] = acc;  // g == (b * (max_lag + 1) + tau) * k + v
+}
+
+// N > kAcMaxLen: the series streams through LDS in tiles as in
+// autocorr_long_kernel; every r_m(tau) is still the ascending sum over i, so
+// the bits equal the short kernel's.
+template <typename T>
+__global__ __launch_bounds__(kCvBlock) void mean_acov_long_kernel(const T* __restrict__ x, int64_t n_chains,
+                                                                 int64_t N, int k, int64_t s_chain, int64_t s_t,
+                                                                 int64_t s_var, const double* __restrict__ mean,
+                                                                 int max_lag, int64_t block_chains,
+                                                                 double* __restrict__ partial) {
+  __shared__ double a[kAcTile];
+  __shared__ double bq[kAcTile + kCvBlock];
+  const int64_t b = blockIdx.x / k;
+  const int v = (int)(blockIdx.x - b * k);
+  const int tau0 = (int)blockIdx.y * kCvBlock;
+  const int sh = (int)threadIdx.x;
+  const int tau = tau0 + sh;
+  const int64_t m0 = b * block_chains;
+  const int64_t m1 = (m0 + block_chains) < 2 * n_chains ? (m0 + block_chains) : 2 * n_chains;
+  double acc = 0.0;
+  for (int64_t m = m0; m < m1; ++m) {
+    const T* src = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
+    const double mu = mean[m * k + v];
+    double r = 0.0;
+    for (int64_t t0 = 0; t0 + tau0 < N; t0 += kAcTile) {
+      for (int i = threadIdx.x; i < kAcTile; i += kCvBlock) {
+        const int64_t t = t0 + i;
+        a[i] = t < N ? (double)src[t * s_t] - mu : 0.0;
+      }
+      for (int i = threadIdx.x; i < kAcTile + kCvBlock; i += kCvBlock) {
+        const int64_t t = t0 + tau0 + i;
+        bq[i] = t < N ? (double)src[t * s_t] - mu : 0.0;
+      }
+      __syncthreads();
+      if (tau <= max_lag) {
+        const int64_t rem = N - tau - t0;  // terms t0 + i with t0 + i + tau < N
+        const int n = rem < kAcTile ? (int)(rem > 0 ? rem : 0) : kAcTile;
+        int i = 0;
+        for (; i + kCvBatch <= n; i += kCvBatch) {
+          double p[kCvBatch];
+#pragma unroll
+          for (int u = 0; u < kCvBatch; ++u) p[u] = a[i + u] * bq[i + u + sh];
+#pragma unroll
+          for (int u = 0; u < kCvBatch; ++u) r = r + p[u];
+        }
+        for (; i < n; ++i) r = r + a[i] * bq[i + sh];
+      }
+      __syncthreads();
+    }
+    if (tau <= max_lag) acc = acc + r / (double)N;
+  }
+  if (tau <= max_lag) partial[(b * ((int64_t)max_lag + 1) + tau) * k + v] = acc;
+}
+
+// keep="moments" sums -> per-chain mean and sample variance, the operations of
+// the host formula in its order: mean = s / n, var = (s2 - (s * s) / n) / (n - 1).
+__global__ __launch_bounds__(kCvBlock) void moments_stats_kernel(const double* __restrict__ sum_u,
+                                                                const double* __restrict__ sum_u2, int64_t count,
+                                                                double n, double* __restrict__ mean_out,
+                                                                double* __restrict__ var_out) {
+  const int64_t g = (int64_t)blockIdx.x * kCvBlock + threadIdx.x;
+  if (g >= count) return;
+  const double s = sum_u[g];
+  mean_out[g] = s / n;
+  var_out[g] = (sum_u2[g] - (s * s) / n) / (n - 1.0);
+}
+
+// block_sums_kernel over (x - center[j])^2: the centred second stage of a
+// two-pass variance across chains, in the same fixed order.
+__global__ __launch_bounds__(kBsThreads) void centered_sq_block_sums_kernel(const double* __restrict__ x,
+                                                                           int64_t n_rows, int64_t k, int64_t stride,
+                                                                           const double* __restrict__ center,
+                                                                           int64_t B, double* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * kBsThreads + threadIdx.x;
+  const int64_t nb = (n_rows + B - 1) / B;
+  if (t >= nb * k) return;
+  const int64_t b = t / k, j = t - b * k;
+  const int64_t r0 = b * B;
+  const int64_t rows = (n_rows - r0) < B ? (n_rows - r0) : B;
+  const double* p = x + r0 * stride + j;
+  const double c = center[j];
+  double s = 0.0;
+  int64_t r = 0;
+  for (; r + kBsUnroll <= rows; r += kBsUnroll) {
+    double d[kBsUnroll];
+#pragma unroll
+    for (int u = 0; u < kBsUnroll; ++u) d[u] = p[(r + u) * stride] - c;
+#pragma unroll
+    for (int u = 0; u < kBsUnroll; ++u) s = s + d[u] * d[u];
+  }
+  for (; r < rows; ++r) {
+    const double d = p[r * stride] - c;
+    s = s + d * d;
+  }
+  out[b * k + j] = s;
+}
+
+// shared argument checks of ipmc_split_stats / ipmc_mean_acov; 0 = launch,
+// -1 = nothing to do, else the status to return
+static int cv_check(const char* fn, const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k,
+                    int64_t s_chain, int64_t s_t, int64_t s_var) {
+  if (n_chains < 0 || len < 0 || k < 0 || s_chain < 0 || s_t < 0 || s_var < 0) {
+    set_error("%s: negative size", fn);
+    return IPMC_ERR_INVALID;
+  }
+  if (n_chains == 0) return -1;
+  if (len < 4) {
+    set_error("%s: %lld samples per chain; a split chain needs at least 2 (len >= 4)", fn, (long long)len);
+    return IPMC_ERR_INVALID;
+  }
+  if (k < 1 || k > 256) {
+    set_error("%s: k = %d outside [1, 256]", fn, k);
+    return IPMC_ERR_INVALID;
+  }
+  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
+    set_error("%s: bad dtype", fn);
+    return IPMC_ERR_INVALID;
+  }
+  if (!x) {
+    set_error("%s: NULL pointer", fn);
+    return IPMC_ERR_INVALID;
+  }
+  if (2 * n_chains > 0x7fffffff / 256) {
+    set_error("%s: at most %d chains per call", fn, 0x7fffffff / 512);
+    return IPMC_ERR_INVALID;
+  }
+  return 0;
+}
+
+}  // namespace ipmc
+
+extern "C" int ipmc_split_stats(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k,
+                                int64_t stride_chain, int64_t stride_t, int64_t stride_var, double* mean_out,
+                                double* var_out, void* stream) {
+  int rc = cv_check("ipmc_split_stats", x, dtype, n_chains, len, k, stride_chain, stride_t, stride_var);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
+  if (!mean_out || !var_out) {
+    set_error("ipmc_split_stats: NULL pointer");
+    return IPMC_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t N = len / 2, series = 2 * n_chains * k;
+  const bool over_time = cv_lanes_over_time(N, k, stride_t);
+  const int64_t per_block = over_time ? kCvBlock / 64 : kCvBlock;
+  const dim3 grid((unsigned)((series + per_block - 1) / per_block)), block(kCvBlock);
+#define IPMC_CV_STATS(KERNEL, T)                                                                              \
+  hipLaunchKernelGGL(KERNEL<T>, grid, block, 0, st, (const T*)x, n_chains, N, (int)k, stride_chain, stride_t, \
+                     stride_var, mean_out, var_out)
+  if (over_time) {
+    if (dtype == IPMC_F64)
+      IPMC_CV_STATS(split_stats_time_kernel, double);
+    else
+      IPMC_CV_STATS(split_stats_time_kernel, float);
+    return check_launch("split_stats_time_kernel");
+  }
+  if (dtype == IPMC_F64)
+    IPMC_CV_STATS(split_stats_vars_kernel, double);
+  else
+    IPMC_CV_STATS(split_stats_vars_kernel, float);
+#undef IPMC_CV_STATS
+  return check_launch("split_stats_vars_kernel");
+}
+
+extern "C" int ipmc_mean_acov(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k,
+                              int64_t stride_chain, int64_t stride_t, int64_t stride_var, const double* mean,
+                              int32_t max_lag, int64_t block_chains, double* partial_out, void* stream) {
+  if (max_lag < 0) {
+    set_error("ipmc_mean_acov: negative size");
+    return IPMC_ERR_INVALID;
+  }
+  int rc = cv_check("ipmc_mean_acov", x, dtype, n_chains, len, k, stride_chain, stride_t, stride_var);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
+  const int64_t N = len / 2;
+  if (max_lag > N - 1) {
+    set_error("ipmc_mean_acov: max_lag %d exceeds len/2 - 1 = %lld", max_lag, (long long)(N - 1));
+    return IPMC_ERR_INVALID;
+  }
+  if (block_chains <= 0) {
+    set_error("ipmc_mean_acov: block_chains must be positive");
+    return IPMC_ERR_INVALID;
+  }
+  if (!mean || !partial_out) {
+    set_error("ipmc_mean_acov: NULL pointer");
+    return IPMC_ERR_INVALID;
+  }
+  const int64_t n_blocks = (2 * n_chains + block_chains - 1) / block_chains;
+  const int64_t tiles = ((int64_t)max_lag + kCvBlock) / kCvBlock;  // ceil((max_lag + 1) / kCvBlock)
+  if (tiles > 65535) {
+    set_error("ipmc_mean_acov: max_lag %d needs more than 65535 lag tiles", max_lag);
+    return IPMC_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)(n_blocks * k), (unsigned)tiles), block(kCvBlock);
+#define IPMC_CV_ACOV(KERNEL, T)                                                                               \
+  hipLaunchKernelGGL(KERNEL<T>, grid, block, 0, st, (const T*)x, n_chains, N, (int)k, stride_chain, stride_t, \
+                     stride_var, mean, (int)max_lag, block_chains, partial_out)
+  if (N <= kCvDirectLen) {
+    const int64_t lanes = n_blocks * ((int64_t)max_lag + 1) * k;
+    const dim3 dgrid((unsigned)((lanes + kCvBlock - 1) / kCvBlock));
+    if (dtype == IPMC_F64)
+      hipLaunchKernelGGL(mean_acov_direct_kernel<double>, dgrid, block, 0, st, (const double*)x, n_chains, N, (int)k,
+                         stride_chain, stride_t, stride_var, mean, (int)max_lag, block_chains, n_blocks, partial_out);
+    else
+      hipLaunchKernelGGL(mean_acov_direct_kernel<float>, dgrid, block, 0, st, (const float*)x, n_chains, N, (int)k,
+                         stride_chain, stride_t, stride_var, mean, (int)max_lag, block_chains, n_blocks, partial_out);
+    return check_launch("mean_acov_direct_kernel");
+  }
+  if (N > kAcMaxLen) {
+    if (dtype == IPMC_F64)
+      IPMC_CV_ACOV(mean_acov_long_kernel, double);
+    else
+      IPMC_CV_ACOV(mean_acov_long_kernel, float);
+    return check_launch("mean_acov_long_kernel");
+  }
+  if (dtype == IPMC_F64)
+    IPMC_CV_ACOV(mean_acov_kernel, double);
+  else
+    IPMC_CV_ACOV(mean_acov_kernel, float);
+#undef IPMC_CV_ACOV
+  return check_launch("mean_acov_kernel");
+}
+
+extern "C" int ipmc_moments_stats(const double* sum_u, const double* sum_u2, int64_t n_chains, int32_t k, int64_t n,
+                                  double* mean_out, double* var_out, void* stream) {
+  if (n_chains < 0 || k < 0 || n < 0) {
+    set_error("ipmc_moments_stats: negative size");
+    return IPMC_ERR_INVALID;
+  }
+  if (n_chains == 0 || k == 0) return IPMC_OK;
+  if (n < 2) {
+    set_error("ipmc_moments_stats: a variance needs n >= 2 steps, got %lld", (long long)n);
+    return IPMC_ERR_INVALID;
+  }
+  if (!sum_u || !sum_u2 || !mean_out || !var_out) {
+    set_error("ipmc_moments_stats: NULL pointer");
+    return IPMC_ERR_INVALID;
+  }
+  const int64_t count = n_chains * k;
+  if ((count + kCvBlock - 1) / kCvBlock > 0x7fffffff) {
+    set_error("ipmc_moments_stats: too many values for one call");
+    return IPMC_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(moments_stats_kernel, dim3((unsigned)((count + kCvBlock - 1) / kCvBlock)), dim3(kCvBlock), 0,
+                     (hipStream_t)stream, sum_u, sum_u2, count, (double)n, mean_out, var_out);
+  return check_launch("moments_stats_kernel");
+}
+
+extern "C" int ipmc_centered_sq_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride,
+                                           const double* center, int64_t block_rows, double* out, void* stream) {
+  if (n_rows < 0 || k < 0 || row_stride < k || block_rows <= 0) {
+    set_error("ipmc_centered_sq_block_sums: bad shape (n_rows, k >= 0, row_stride >= k, block_rows > 0)");
+    return IPMC_ERR_INVALID;
+  }
+  if (n_rows == 0 || k == 0) return IPMC_OK;
+  if (!rows || !center || !out) {
+    set_error("ipmc_centered_sq_block_sums: NULL pointer");
+    return IPMC_ERR_INVALID;
+  }
+  const int64_t lanes = (n_rows + block_rows - 1) / block_rows * k;
+  hipLaunchKernelGGL(centered_sq_block_sums_kernel, dim3((unsigned)((lanes + kBsThreads - 1) / kBsThreads)),
+                     dim3(kBsThreads), 0, (hipStream_t)stream, rows, n_rows, k, row_stride, center, block_rows, out);
+  return check_launch("centered_sq_block_sums_kernel");
+}
