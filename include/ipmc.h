@@ -36,6 +36,9 @@
  *                                                             ipmc_split_stats, ipmc_mean_acov,
  *                                                             ipmc_moments_stats, ipmc_centered_sq_block_sums
  *                                                             (split-R-hat, ESS and MCSE over the ensemble)
+ *   wasserstein_distance's inputs     helpers.py:57-77,       ipmc_minmax, ipmc_hist1d, ipmc_histdd
+ *   (intervals from the data's min    burgers_wasserstein_    (support, marginal and joint np.histogramdd
+ *   and max, np.histogramdd)          chain.py:169-188        counts pooled over all chains, on the device)
  *
  * The reference has no FFI of its own (it is duck-typed Python); these entry
  * points are what a ctypes binding of its plugin API binds.
@@ -313,6 +316,39 @@ int ipmc_moments_stats(const double* sum_u, const double* sum_u2, int64_t n_chai
    center: double [k]; out: double [ceil(n_rows / block_rows), k]. */
 int ipmc_centered_sq_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride,
                                 const double* center, int64_t block_rows, double* out, void* stream);
+
+/* Pooled posterior histograms (posterior.support / marginal_histograms / histogramdd: the binning of
+   burgers_wasserstein_chain.py:169-188 for helpers.py:57-77's distance).  Additive to ABI 13.
+   The samples have ipmc_split_stats' geometry: sample t of component v of chain c is
+   x[c*stride_chain + t*stride_t + v*stride_var], t < len, 1 <= k <= 256, float or double (widened to double
+   before any comparison).  All chains and samples are pooled.  n_chains == 0 is a no-op.  Counters are
+   integers (int64 results, no floating-point atomics), so no result depends on the grid or on arrival order.
+   Bin b of B holds x iff edges[b] <= x < edges[b+1], the last bin also x == edges[B]; edges ascending doubles.
+
+   ipmc_minmax: min_out[v], max_out[v] = min and max over every sample of component v, double [k] each; NaN is
+   skipped, a component without a comparable sample gives (+inf, -inf).  Per-workgroup partials in `scratch`
+   (device, double [2 * IPMC_MINMAX_GROUPS * k], overwritten), combined by a second kernel: no atomics. */
+#define IPMC_MINMAX_GROUPS 1024
+int ipmc_minmax(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
+                int64_t stride_t, int64_t stride_var, double* min_out, double* max_out, double* scratch,
+                void* stream);
+
+/* counts[v, b] = samples of component v in bin b of edges[v, 0..bins] (double [k, bins + 1], 1 <= bins <= 4096),
+   below[v] = those < edges[v, 0], above[v] = those > edges[v, bins]; NaN counts nowhere.  counts int64 [k, bins],
+   below / above int64 [k]; all three are zeroed on `stream` by the call itself. */
+int ipmc_hist1d(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
+                int64_t stride_t, int64_t stride_var, int32_t bins, const double* edges, int64_t* counts,
+                int64_t* below, int64_t* above, void* stream);
+
+/* Joint counts over the nd <= 4 components comp[0..nd) with bins[d] bins each (1 <= bins[d] <= 4096, at most
+   2^24 cells in all): counts[b_0, ..., b_nd-1] row-major, int64, zeroed on `stream` by the call.  A sample counts
+   iff every selected component is inside its edges (np.histogramdd).  edges: the axes' edge arrays one after
+   the other, double [sum(bins[d] + 1)], on the device.  comp and bins are HOST arrays of nd int32, read
+   during the call (the one exception to the device-pointer convention above).  Up to 8192 cells are counted
+   in LDS, more by 64-bit integer adds in global memory. */
+int ipmc_histdd(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
+                int64_t stride_t, int64_t stride_var, int32_t nd, const int32_t* comp, const int32_t* bins,
+                const double* edges, int64_t* counts, void* stream);
 
 /* Lorenz-96 layout of a ONE-step launch (no speculation) when lanes_per_chain = chains_per_lane = 0:
    returns lanes_per_chain, and chains_per_lane * 100 + lanes_per_chain from ipmc_auto_layout.

@@ -40,11 +40,20 @@ from .rng import PhiloxRNG, PhiloxStream
 pCNProposer = ConstSteppCNProposer
 from ._lib import IpmcError, UnsupportedOnDevice
 from .diagnostics import convergence, moments_convergence, split_rhat
+from .posterior import (hist_quantiles, histogramdd, marginal_histograms, support, wasserstein_1d,
+                        wasserstein_distance, wasserstein_to_point)
 
 __all__ = [
     "convergence",
     "split_rhat",
     "moments_convergence",
+    "support",
+    "marginal_histograms",
+    "histogramdd",
+    "hist_quantiles",
+    "wasserstein_to_point",
+    "wasserstein_1d",
+    "wasserstein_distance",
     "MCMCSampler",
     "ProposerBase",
     "ConstSteppCNProposer",

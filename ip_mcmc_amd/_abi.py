@@ -148,6 +148,21 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "ipmc_centered_sq_block_sums": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_void_p]),
+    "ipmc_minmax": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "ipmc_hist1d": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "ipmc_histdd": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
     "ipmc_auto_lanes": (C.c_int, [C.POINTER(IpmcModel), C.c_int32, C.c_int64]),
     "ipmc_auto_layout": (C.c_int, [C.POINTER(IpmcModel), C.c_int32, C.c_int64]),
     "ipmc_plan_sweep": (C.c_int, [C.POINTER(IpmcModel), C.POINTER(IpmcSweep), C.POINTER(IpmcPlan)]),
