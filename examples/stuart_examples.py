@@ -15,10 +15,14 @@ are pooled and compared with the exact Gaussian posterior
 
   python examples/stuart_examples.py [chains]
 
-Prints one JSON line per example: posterior mean and variance of the pooled
-samples, the exact values, the deviation of the mean in Monte-Carlo standard
-errors (per-chain means, so autocorrelation is accounted for), accept rate and
-wall time.
+A third run is config 1, G(u) = <g, u> with g = [3, 1, 4, 1] (k = 4, u_true =
+[2, 7, 1, 8]): its posterior covariance Σ0 − Σ0g gᵀΣ0/(γ² + gᵀΣ0g) differs from
+the prior's only by a rank-one term, mostly off the diagonal.
+
+Prints one JSON line per example: posterior mean, variance and covariance
+matrix (posterior_covariance, on the device) of the pooled samples, the exact
+values, the deviation of the mean in Monte-Carlo standard errors (per-chain
+means, so autocorrelation is accounted for), accept rate and wall time.
 """
 import json
 import os
@@ -29,7 +33,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ip_mcmc_amd import (ConstSteppCNProposer, CountedAccepter, EvolutionPotential,  # noqa: E402
-                         GaussianDistribution, LinearOperator, MCMCSampler, pCNAccepter)
+                         GaussianDistribution, LinearOperator, MCMCSampler, pCNAccepter, posterior_covariance)
 
 
 def digits(x, n):
@@ -68,6 +72,8 @@ def run_example(name, A, u_true, gamma, noise, chains, n_samples=5000, beta=0.25
         "mean_error_in_mcse": ((pooled.mean(axis=0) - mean) / mcse).tolist(),
         "posterior_var": pooled.var(axis=0).tolist(),
         "exact_var": np.diag(cov).tolist(),
+        "posterior_cov": posterior_covariance(samples)["cov"].tolist(),
+        "exact_cov": cov.tolist(),
         "accept_rate": float(np.mean(accepter.ratio())),
         "pcn_steps_per_s": chains * (1000 + n_samples * 200) / wall,
         "wall_s": wall,
@@ -86,6 +92,11 @@ def main():
     print(json.dumps(run_example("2.2", g2.reshape(2, 1), np.array([0.5]), gamma,
                                  GaussianDistribution(mean=np.zeros(2), covariance=np.identity(2) * gamma**2),
                                  chains)), flush=True)
+    # config 1: G(u) = <g, u> with g = [3, 1, 4, 1], k = 4: one observation leaves the posterior's
+    # information in the off-diagonal entries of its covariance (posterior_cov against exact_cov)
+    g4 = digits(np.pi, 4).astype(float)
+    print(json.dumps(run_example("config1", g4.reshape(1, 4), digits(np.e, 4).astype(float), gamma,
+                                 GaussianDistribution(mean=0, covariance=gamma**2), chains)), flush=True)
 
 
 if __name__ == "__main__":

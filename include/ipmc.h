@@ -39,6 +39,8 @@
  *   wasserstein_distance's inputs     helpers.py:57-77,       ipmc_minmax, ipmc_hist1d, ipmc_histdd
  *   (intervals from the data's min    burgers_wasserstein_    (support, marginal and joint np.histogramdd
  *   and max, np.histogramdd)          chain.py:169-188        counts pooled over all chains, on the device)
+ *   the exact posterior covariance    results.org:59-62       ipmc_scatter (pooled covariance and the k x k
+ *   the studies are compared with                             within / between covariance of the split chains)
  *
  * The reference has no FFI of its own (it is duck-typed Python); these entry
  * points are what a ctypes binding of its plugin API binds.
@@ -349,6 +351,26 @@ int ipmc_hist1d(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int
 int ipmc_histdd(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
                 int64_t stride_t, int64_t stride_var, int32_t nd, const int32_t* comp, const int32_t* bins,
                 const double* edges, int64_t* counts, void* stream);
+
+/* Pooled second moments between components (covariance.posterior_covariance / multivariate_rhat).  Additive
+   to ABI 13.  The samples have ipmc_split_stats' geometry (float or double, widened to double on load).
+   scatter_out[b, i, j] = Σ (x_i - c_i)(x_j - c_j) and dsum_out[b, i] = Σ (x_i - c_i) over the rows of the chains
+   of block b (block_chains consecutive whole chains, the last block possibly shorter), each block from zero;
+   scatter_out double [ceil(n_chains / block_chains), k, k], dsum_out double [., k] or NULL.
+   center_mode 0 (IPMC_CENTER_SHARED): center is double [k]; all len >= 1 rows of every chain are used.
+   center_mode 1 (IPMC_CENTER_SPLIT): center is double [2*n_chains, k], ipmc_split_stats' mean_out; with
+   N = len/2, rows t < N of chain c use center[c], rows N <= t < 2N use center[n_chains + c], row 2N (odd
+   len) is skipped; len >= 4.
+   Both triangles are written from one computed value: [b, i, j] and [b, j, i] hold the same bits.  One
+   workgroup per (block, pair of column tiles); inside a block the order of the fused multiply-adds is a
+   function of (k, len, strides' order, block_chains) alone -- no floating-point atomics, nothing depends on
+   the grid, the occupancy or arrival order, so two calls give the same bits.  A NaN sample makes only the
+   rows and columns of its component NaN.  n_chains == 0 is a no-op. */
+#define IPMC_CENTER_SHARED 0
+#define IPMC_CENTER_SPLIT 1
+int ipmc_scatter(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
+                 int64_t stride_t, int64_t stride_var, const double* center, int32_t center_mode,
+                 int64_t block_chains, double* scatter_out, double* dsum_out, void* stream);
 
 /* Lorenz-96 layout of a ONE-step launch (no speculation) when lanes_per_chain = chains_per_lane = 0:
    returns lanes_per_chain, and chains_per_lane * 100 + lanes_per_chain from ipmc_auto_layout.

@@ -40,6 +40,7 @@ from .rng import PhiloxRNG, PhiloxStream
 pCNProposer = ConstSteppCNProposer
 from ._lib import IpmcError, UnsupportedOnDevice
 from .diagnostics import convergence, moments_convergence, split_rhat
+from .covariance import multivariate_rhat, posterior_covariance
 from .posterior import (hist_quantiles, histogramdd, marginal_histograms, support, wasserstein_1d,
                         wasserstein_distance, wasserstein_to_point)
 
@@ -54,6 +55,8 @@ __all__ = [
     "wasserstein_to_point",
     "wasserstein_1d",
     "wasserstein_distance",
+    "posterior_covariance",
+    "multivariate_rhat",
     "MCMCSampler",
     "ProposerBase",
     "ConstSteppCNProposer",

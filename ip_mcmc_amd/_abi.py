@@ -12,6 +12,7 @@ MODEL_LINEAR, MODEL_LORENZ63, MODEL_LORENZ96, MODEL_BURGERS, MODEL_LORENZ96_2S =
 ARITH_FMA, ARITH_REFERENCE = 0, 1
 DT_FIXED, DT_CFL = 0, 1
 PROPOSAL_PCN, PROPOSAL_RW = 0, 1
+CENTER_SHARED, CENTER_SPLIT = 0, 1
 
 STATUS_NAMES = {
     OK: "IPMC_OK",
@@ -162,6 +163,11 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "ipmc_scatter": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+         C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
     "ipmc_auto_lanes": (C.c_int, [C.POINTER(IpmcModel), C.c_int32, C.c_int64]),
     "ipmc_auto_layout": (C.c_int, [C.POINTER(IpmcModel), C.c_int32, C.c_int64]),
