@@ -291,8 +291,9 @@ int ipmc_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_s
    m - n_chains otherwise.  No floating-point atomics; every sum has a fixed order that depends on the
    arguments alone, so two calls give the same bits.  n_chains == 0 is a no-op; len < 4 is invalid.
 
-   ipmc_split_stats: mean_out[m, v] = mean of the split chain, var_out[m, v] = Σ (x - mean)² / (N - 1)
-   (two passes, centred); both double [2*n_chains, k]. */
+   ipmc_split_stats: mean_out[m, v] = mean of the split chain, summed about its first sample
+   (x_0 + Σ (x_t - x_0) / N), var_out[m, v] = Σ (x - mean)² / (N - 1) (two passes, centred); both
+   double [2*n_chains, k]. */
 int ipmc_split_stats(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
                      int64_t stride_t, int64_t stride_var, double* mean_out, double* var_out, void* stream);
 

@@ -50,7 +50,7 @@ import torch
 from . import _abi
 from . import device as dev
 from ._lib import call
-from .diagnostics import SUM_BLOCK, _check_layout, _is_cuda, _on_device, _ordered_col_sums, _seq_sum
+from .diagnostics import SUM_BLOCK, _check_layout, _is_cuda, _on_device, _ordered_col_sums, _pivot_mean, _seq_sum
 from .posterior import DEFAULT_CHUNK_BYTES, _as3d, _geom, _host_cnk, _shape
 
 PARTIAL_BYTES = 256 << 20  # the block partials [nb, k, k] stay below this with the default block
@@ -119,9 +119,11 @@ def _host_split_means(x, layout, block):
     N = _shape(x, layout)[1] // 2
     first, second = [], []
     for c0 in range(0, x.shape[0], block):
-        xb = _host_cnk(x[c0:c0 + block], layout)
-        first.append(xb[:, :N].mean(axis=1))
-        second.append(xb[:, N:2 * N].mean(axis=1))
+        # one memory order, as diagnostics._host_samples (numpy adds a strided axis in sample order and a
+        # contiguous one pairwise), and diagnostics' means about the first sample
+        xb = np.ascontiguousarray(_host_cnk(x[c0:c0 + block], layout))
+        first.append(_pivot_mean(xb[:, :N]))
+        second.append(_pivot_mean(xb[:, N:2 * N]))
     return np.concatenate(first + second, axis=0)
 
 

@@ -515,6 +515,11 @@ extern "C" int ipmc_autocorr(const void* x, int32_t dtype, int64_t n_series, int
 //                    then a fixed xor butterfly (32, 16, ..., 1): for k = 2..3
 //                    with many samples the waves of one block share the lines
 //                    they read, and with unit time stride the loads are dense.
+// The mean is summed about the series' first sample, mean = x_0 + Σ (x_t - x_0) / N:
+// the differences are spread-sized, so the rounding of the sum is far below
+// an ulp of a mean that is many spreads large, and both mappings (and the
+// host definition, in sample order) round the same value: Bn, the covariance
+// of such means, multiplies a change of a mean by 2 |mean| / spread.
 namespace ipmc {
 
 constexpr int kCvBlock = 256;
@@ -549,10 +554,11 @@ __global__ __launch_bounds__(kCvBlock) void split_stats_vars_kernel(const T* __r
   const int64_t m = g / k;
   const int v = (int)(g - m * k);
   const T* a = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
+  const double x0 = (double)a[0];
   double s = 0.0;
 #pragma unroll 8
-  for (int64_t t = 0; t < N; ++t) s = s + (double)a[t * s_t];
-  const double mean = s / (double)N;
+  for (int64_t t = 0; t < N; ++t) s = s + ((double)a[t * s_t] - x0);
+  const double mean = x0 + s / (double)N;
   double q = 0.0;
 #pragma unroll 8
   for (int64_t t = 0; t < N; ++t) {
@@ -574,9 +580,10 @@ __global__ __launch_bounds__(kCvBlock) void split_stats_time_kernel(const T* __r
   const int64_t m = g / k;
   const int v = (int)(g - m * k);
   const T* a = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
+  const double x0 = (double)a[0];
   double s = 0.0;
-  for (int64_t t = lane; t < N; t += 64) s = s + (double)a[t * s_t];
-  const double mean = cv_wave_sum(s) / (double)N;
+  for (int64_t t = lane; t < N; t += 64) s = s + ((double)a[t * s_t] - x0);
+  const double mean = x0 + cv_wave_sum(s) / (double)N;
   double q = 0.0;
   for (int64_t t = lane; t < N; t += 64) {
     const double d = (double)a[t * s_t] - mean;

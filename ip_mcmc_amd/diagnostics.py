@@ -199,13 +199,23 @@ def _host_samples(samples, layout):
     return np.ascontiguousarray(a.transpose(0, 2, 1) if layout == "vars_time" else a)
 
 
+def _pivot_mean(S):
+    """Means over axis 1 of (M, N, k), summed about each series' first sample: x_0 + Σ (x_t − x_0)/N.
+    The differences are spread-sized, so the sum's rounding is far below an ulp of a mean that is
+    many spreads large (θ = 8 + u; 10⁵ standard deviations in the tests), and any order of the adds
+    rounds the same value: B/N, the variance of such means, multiplies a change of a mean by
+    2 |mean| / spread.  ipmc_split_stats sums the same way."""
+    x0 = S[:, :1]
+    return x0[:, 0] + (S - x0).mean(axis=1)
+
+
 def _host_parts(x, max_lag=None):
     """The sums of the definition on float64 (C, n, k): (mean (k,), W (k,),
     B/N (k,), mean_m γ_m(t) (max_lag + 1, k) or None when max_lag is None)."""
     C, n, k = x.shape
     N, M = n // 2, 2 * C
     S = np.concatenate([x[:, :N], x[:, N:2 * N]], axis=0)  # (M, N, k)
-    mu = S.mean(axis=1)
+    mu = _pivot_mean(S)
     d = S - mu[:, None, :]
     s2 = (d * d).sum(axis=1) / (N - 1)
     mean = mu.mean(axis=0)

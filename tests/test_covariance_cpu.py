@@ -11,6 +11,11 @@ from ip_mcmc_amd.covariance import default_block_chains
 # a short last block, the minimum
 SHAPES = [(5, 13, 3, None), (3, 10, 40, None), (2, 6, 256, None), (7, 9, 17, None), (70, 8, 5, 16), (1, 2, 1, None)]
 IDS = ["-".join(str(v) for v in s) for s in SHAPES]
+# the shapes on which tests/test_gpu_covariance_slabs.py runs the API on the device against this
+# definition (several slabs per block, partial last tiles); the last one takes the default block
+SLAB_SHAPES = [(7, 53, 65, 7), (5, 61, 129, 5), (9, 29, 200, 4), (3, 71, 255, 3), (11, 19, 256, 11), (8, 24, 256, 8),
+               (7, 53, 65, None)]
+SLAB_IDS = ["-".join(str(v) for v in s) for s in SLAB_SHAPES]
 
 
 def make_samples(C, n, k, seed=0, dtype=np.float64, layout="time_vars", offset=1e5, sd_lo=0.01):
@@ -39,7 +44,7 @@ def assert_cov_close(got, want, rel):
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("layout", ["time_vars", "vars_time"])
-@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+@pytest.mark.parametrize("shape", SHAPES + SLAB_SHAPES, ids=IDS + SLAB_IDS)
 def test_host_definition_equals_numpy(shape, layout, dtype):
     C, n, k, block = shape
     x = make_samples(C, n, k, seed=k + n, dtype=dtype, layout=layout)
@@ -51,6 +56,43 @@ def test_host_definition_equals_numpy(shape, layout, dtype):
     m = p.mean(axis=0)
     assert np.all(np.abs(r["mean"] - m) <= 1e-14 * np.abs(m))
     assert np.all(np.abs(r["corr"] - np.atleast_2d(np.corrcoef(p, rowvar=False))) <= 1e-12)
+
+
+@pytest.mark.parametrize("shape", SLAB_SHAPES, ids=SLAB_IDS)
+def test_host_definition_does_not_depend_on_the_layout(shape):
+    """The same samples as (C, n, k) and as (C, k, n) give the same bits: the split-chain means are
+    added in sample order in both.  numpy adds a contiguous axis pairwise from 8 terms on, and Bn of
+    chain means of 10⁵ standard deviations moves by 1e-10 when a mean moves in its last bits."""
+    C, n, k, block = shape
+    x = make_samples(C, n, k, seed=k + n)
+    xt = np.ascontiguousarray(x.transpose(0, 2, 1))
+    a = posterior_covariance(x, backend="host", block_chains=block)
+    b = posterior_covariance(xt, layout="vars_time", backend="host", block_chains=block)
+    for key in ("mean", "cov", "corr"):
+        assert np.array_equal(a[key], b[key]), key
+    ra = multivariate_rhat(x, backend="host", block_chains=block)
+    rb = multivariate_rhat(xt, layout="vars_time", backend="host", block_chains=block)
+    for key in ("W", "Bn", "rhat"):
+        assert np.array_equal(ra[key], rb[key]), key
+
+
+def test_split_chain_means_do_not_depend_on_the_order_of_the_adds():
+    """Means summed about the first sample (diagnostics._pivot_mean, as ipmc_split_stats): the
+    differences are spread-sized, so sample order and numpy's pairwise order round the same mean,
+    within 1 ulp of the exact one; plain sums of numbers 1e5 spreads large are up to 6 ulp off."""
+    import math
+
+    from ip_mcmc_amd.diagnostics import _pivot_mean
+
+    x = make_samples(3, 71, 255, seed=326)
+    S = np.concatenate([x[:, :35], x[:, 35:70]], axis=0)
+    mu = _pivot_mean(S)
+    d = S - S[:, :1]
+    pairwise = S[:, 0] + np.ascontiguousarray(d.transpose(0, 2, 1)).sum(axis=2) / 35
+    assert np.array_equal(mu, pairwise)
+    exact = np.array([[math.fsum(S[m, :, v]) / 35 for v in range(255)] for m in range(6)])
+    assert np.all(np.abs(mu - exact) <= np.spacing(exact))
+    assert np.any(np.abs(S.mean(axis=1) - exact) > 2 * np.spacing(exact))  # the plain sum is not
 
 
 def test_the_tolerance_rejects_the_one_pass_form():

@@ -21,6 +21,7 @@ import torch
 
 from ip_mcmc_amd import _abi, multivariate_rhat, posterior_covariance
 from ip_mcmc_amd._lib import call
+from ip_mcmc_amd.posterior import _geom
 from test_covariance_cpu import IDS, SHAPES, assert_cov_close, make_samples
 
 pytestmark = pytest.mark.gpu
@@ -132,14 +133,17 @@ def test_chunked_host_input_gives_the_bits_of_one_chunk(layout):
     assert_same_cov(one, posterior_covariance(x, layout=layout, backend="host", block_chains=16))
 
 
-def _scatter(t, center, mode, block, with_dsum=True):
-    """ipmc_scatter on a contiguous (C, n, k) device tensor: (scatter [nb, k, k], dsum [nb, k])."""
-    C, n, k = t.shape
+def _scatter(t, center, mode, block, with_dsum=True, layout="time_vars"):
+    """ipmc_scatter on a 3-D device tensor, (C, n, k) or (C, k, n) with layout="vars_time", f64 or
+    f32, contiguous or a view: it goes to the kernel by the geometry covariance.py passes
+    (posterior._geom), never copied.  Returns (scatter [nb, k, k], dsum [nb, k] or None); both
+    are NaN where the kernel wrote nothing."""
+    geom = _geom(t, layout)
+    C, k = geom[2], geom[4]
     nb = -(-C // block)
     out = torch.full((nb, k, k), np.nan, dtype=torch.float64, device=t.device)
     ds = torch.full((nb, k), np.nan, dtype=torch.float64, device=t.device) if with_dsum else None
-    call("ipmc_scatter", t.data_ptr(), _abi.F64 if t.dtype == torch.float64 else _abi.F32, C, n, k, n * k, k, 1,
-         center.data_ptr(), mode, block, out.data_ptr(), None if ds is None else ds.data_ptr(),
+    call("ipmc_scatter", *geom, center.data_ptr(), mode, block, out.data_ptr(), None if ds is None else ds.data_ptr(),
          torch.cuda.current_stream(t.device).cuda_stream)
     return out.cpu().numpy(), None if ds is None else ds.cpu().numpy()
 
