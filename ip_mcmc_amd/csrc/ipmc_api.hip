@@ -221,21 +221,26 @@ static int l96_plan(const ipmc_model& m, const ipmc_sweep& s, int& lpc, int& cpl
   return IPMC_OK;
 }
 
-template <typename T, int MODEL, bool FM>
-static int small_sweep_launch(const ipmc_model& m, const ipmc_sweep& s, hipStream_t st) {
-  const int64_t blocks = (s.n_chains + kSmallBlock - 1) / kSmallBlock;
-  hipLaunchKernelGGL((small_sweep_kernel<T, MODEL, FM>), dim3((unsigned)blocks), dim3(kSmallBlock), 0, st, m, s);
-  return check_launch("small_sweep_kernel");
+// The template arguments of the small-model kernels (linear, Lorenz-63) for a
+// model and an element type: f(T{}, MODEL, FM), the last two as integral constants.
+template <typename F>
+static int with_small_model(const ipmc_model& m, int32_t dtype, F&& f) {
+  return with_dtype(dtype, [&](auto tag) {
+    return with_bool(m.arith == IPMC_ARITH_FMA, [&](auto fm) {
+      if (m.kind == IPMC_MODEL_LORENZ63) return f(tag, std::integral_constant<int, IPMC_MODEL_LORENZ63>{}, fm);
+      return f(tag, std::integral_constant<int, IPMC_MODEL_LINEAR>{}, fm);
+    });
+  });
 }
 
-template <typename T>
 static int small_sweep(const ipmc_model& m, const ipmc_sweep& s, hipStream_t st) {
-  const bool fm = m.arith == IPMC_ARITH_FMA;
-  if (m.kind == IPMC_MODEL_LORENZ63)
-    return fm ? small_sweep_launch<T, IPMC_MODEL_LORENZ63, true>(m, s, st)
-              : small_sweep_launch<T, IPMC_MODEL_LORENZ63, false>(m, s, st);
-  return fm ? small_sweep_launch<T, IPMC_MODEL_LINEAR, true>(m, s, st)
-            : small_sweep_launch<T, IPMC_MODEL_LINEAR, false>(m, s, st);
+  return with_small_model(m, s.dtype, [&](auto tag, auto model, auto fm) {
+    using T = decltype(tag);
+    const int64_t blocks = (s.n_chains + kSmallBlock - 1) / kSmallBlock;
+    hipLaunchKernelGGL((small_sweep_kernel<T, decltype(model)::value, decltype(fm)::value>), dim3((unsigned)blocks),
+                       dim3(kSmallBlock), 0, st, m, s);
+    return check_launch("small_sweep_kernel");
+  });
 }
 
 // Speculation width for the small models (lanes per chain, small_spec_kernel):
@@ -258,53 +263,35 @@ static int small_spec_width(const ipmc_model& m, const ipmc_sweep& s) {
   return w;
 }
 
-template <typename T, int MODEL, bool FM>
-static int small_spec_launch(const ipmc_model& m, const ipmc_sweep& s, int w, hipStream_t st) {
-  const int64_t blocks = (s.n_chains * w + kSpecBlock - 1) / kSpecBlock;
-  switch (w) {
-#define IPMC_SPEC(W)                                                                                           \
-  case W:                                                                                                      \
-    hipLaunchKernelGGL((small_spec_kernel<T, MODEL, FM, W>), dim3((unsigned)blocks), dim3(kSpecBlock), 0, st, m, \
-                       s);                                                                                     \
-    return check_launch("small_spec_kernel");
-    IPMC_SPEC(2) IPMC_SPEC(4) IPMC_SPEC(8) IPMC_SPEC(16) IPMC_SPEC(32) IPMC_SPEC(64)
-#undef IPMC_SPEC
-  }
-  return fail(IPMC_ERR_UNSUPPORTED, "speculation width must be a power of two <= 64");
-}
-
-template <typename T>
 static int small_spec(const ipmc_model& m, const ipmc_sweep& s, int w, hipStream_t st) {
-  const bool fm = m.arith == IPMC_ARITH_FMA;
-  if (m.kind == IPMC_MODEL_LORENZ63)
-    return fm ? small_spec_launch<T, IPMC_MODEL_LORENZ63, true>(m, s, w, st)
-              : small_spec_launch<T, IPMC_MODEL_LORENZ63, false>(m, s, w, st);
-  return fm ? small_spec_launch<T, IPMC_MODEL_LINEAR, true>(m, s, w, st)
-            : small_spec_launch<T, IPMC_MODEL_LINEAR, false>(m, s, w, st);
+  return with_small_model(m, s.dtype, [&](auto tag, auto model, auto fm) {
+    using T = decltype(tag);
+    const int64_t blocks = (s.n_chains * w + kSpecBlock - 1) / kSpecBlock;
+    switch (w) {
+#define IPMC_SPEC(W)                                                                                        \
+  case W:                                                                                                   \
+    hipLaunchKernelGGL((small_spec_kernel<T, decltype(model)::value, decltype(fm)::value, W>),              \
+                       dim3((unsigned)blocks), dim3(kSpecBlock), 0, st, m, s);                              \
+    return check_launch("small_spec_kernel");
+      IPMC_SPEC(2) IPMC_SPEC(4) IPMC_SPEC(8) IPMC_SPEC(16) IPMC_SPEC(32) IPMC_SPEC(64)
+#undef IPMC_SPEC
+    }
+    return fail(IPMC_ERR_UNSUPPORTED, "speculation width must be a power of two <= 64");
+  });
 }
 
-template <typename T, int MODEL, bool FM>
-static int small_eval_launch(const ipmc_model& m, int64_t n, const void* u, const void* y, const void* ginv,
-                             void* out, bool phi, hipStream_t st) {
-  const int64_t blocks = (n + kSmallBlock - 1) / kSmallBlock;
-  if (phi)
-    hipLaunchKernelGGL((small_eval_kernel<T, MODEL, FM, true>), dim3((unsigned)blocks), dim3(kSmallBlock), 0, st, m,
-                       n, (const T*)u, (const T*)y, (const T*)ginv, (T*)out);
-  else
-    hipLaunchKernelGGL((small_eval_kernel<T, MODEL, FM, false>), dim3((unsigned)blocks), dim3(kSmallBlock), 0, st, m,
-                       n, (const T*)u, (const T*)y, (const T*)ginv, (T*)out);
-  return check_launch("small_eval_kernel");
-}
-
-template <typename T>
-static int small_eval(const ipmc_model& m, int64_t n, const void* u, const void* y, const void* ginv, void* out,
-                      bool phi, hipStream_t st) {
-  const bool fm = m.arith == IPMC_ARITH_FMA;
-  if (m.kind == IPMC_MODEL_LORENZ63)
-    return fm ? small_eval_launch<T, IPMC_MODEL_LORENZ63, true>(m, n, u, y, ginv, out, phi, st)
-              : small_eval_launch<T, IPMC_MODEL_LORENZ63, false>(m, n, u, y, ginv, out, phi, st);
-  return fm ? small_eval_launch<T, IPMC_MODEL_LINEAR, true>(m, n, u, y, ginv, out, phi, st)
-            : small_eval_launch<T, IPMC_MODEL_LINEAR, false>(m, n, u, y, ginv, out, phi, st);
+static int small_eval(const ipmc_model& m, int32_t dtype, int64_t n, const void* u, const void* y, const void* ginv,
+                      void* out, bool phi, hipStream_t st) {
+  return with_small_model(m, dtype, [&](auto tag, auto model, auto fm) {
+    using T = decltype(tag);
+    const int64_t blocks = (n + kSmallBlock - 1) / kSmallBlock;
+    with_bool(phi, [&](auto pot) {
+      hipLaunchKernelGGL((small_eval_kernel<T, decltype(model)::value, decltype(fm)::value, decltype(pot)::value>),
+                         dim3((unsigned)blocks), dim3(kSmallBlock), 0, st, m, n, (const T*)u, (const T*)y,
+                         (const T*)ginv, (T*)out);
+    });
+    return check_launch("small_eval_kernel");
+  });
 }
 
 template <typename T>
@@ -365,8 +352,7 @@ static int dispatch_eval(const ipmc_model* m, int32_t dtype, int64_t n, const vo
   switch (m->kind) {
     case IPMC_MODEL_LINEAR:
     case IPMC_MODEL_LORENZ63:
-      return dtype == IPMC_F64 ? small_eval<double>(*m, n, u, y, ginv, out, phi, st)
-                               : small_eval<float>(*m, n, u, y, ginv, out, phi, st);
+      return small_eval(*m, dtype, n, u, y, ginv, out, phi, st);
     case IPMC_MODEL_LORENZ96: {
       int lpc, cpl;
       l96_layout(m->dim, IPMC_F64, n, lpc, cpl);  // eval kernels run one chain per lane group
@@ -494,8 +480,7 @@ int ipmc_pcn_sweep(const ipmc_model* m, const ipmc_sweep* s, void* stream) {
       const int w = small_spec_width(*m, *s);
       if (w < 0)
         return fail(IPMC_ERR_UNSUPPORTED, "small models: spec_width must be a power of two <= 64, and 1 for k > 8");
-      if (w > 1) return s->dtype == IPMC_F64 ? small_spec<double>(*m, *s, w, st) : small_spec<float>(*m, *s, w, st);
-      return s->dtype == IPMC_F64 ? small_sweep<double>(*m, *s, st) : small_sweep<float>(*m, *s, st);
+      return w > 1 ? small_spec(*m, *s, w, st) : small_sweep(*m, *s, st);
     }
     case IPMC_MODEL_LORENZ96: {
       int lpc, cpl, spec;
@@ -539,23 +524,13 @@ int ipmc_init_phi(const ipmc_model* m, const ipmc_sweep* s, void* stream) {
   int rc = dispatch_eval(m, s->dtype, s->n_chains, s->u, s->y, s->gamma_inv, s->phi, true, stream);
   if (rc || !s->reg_scale || s->n_chains == 0) return rc;
   const int64_t blocks = (s->n_chains + 255) / 256;
-  const bool fm = m->arith == IPMC_ARITH_FMA;
-  hipStream_t st = (hipStream_t)stream;
-  if (s->dtype == IPMC_F64) {
-    if (fm)
-      hipLaunchKernelGGL((reg_add_kernel<double, true>), dim3((unsigned)blocks), dim3(256), 0, st, s->n_chains, m->k,
-                         (const double*)s->u, (const double*)s->reg_scale, (double*)s->phi);
-    else
-      hipLaunchKernelGGL((reg_add_kernel<double, false>), dim3((unsigned)blocks), dim3(256), 0, st, s->n_chains,
-                         m->k, (const double*)s->u, (const double*)s->reg_scale, (double*)s->phi);
-  } else {
-    if (fm)
-      hipLaunchKernelGGL((reg_add_kernel<float, true>), dim3((unsigned)blocks), dim3(256), 0, st, s->n_chains, m->k,
-                         (const float*)s->u, (const float*)s->reg_scale, (float*)s->phi);
-    else
-      hipLaunchKernelGGL((reg_add_kernel<float, false>), dim3((unsigned)blocks), dim3(256), 0, st, s->n_chains,
-                         m->k, (const float*)s->u, (const float*)s->reg_scale, (float*)s->phi);
-  }
+  with_dtype(s->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    with_bool(m->arith == IPMC_ARITH_FMA, [&](auto fm) {
+      hipLaunchKernelGGL((reg_add_kernel<T, decltype(fm)::value>), dim3((unsigned)blocks), dim3(256), 0,
+                         (hipStream_t)stream, s->n_chains, m->k, (const T*)s->u, (const T*)s->reg_scale, (T*)s->phi);
+    });
+  });
   return check_launch("reg_add_kernel");
 }
 
@@ -578,12 +553,11 @@ int ipmc_normal(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t 
   if (total == 0) return IPMC_OK;
   if (!out) return fail(IPMC_ERR_INVALID, "out is NULL");
   const int64_t blocks = (total + 255) / 256;
-  if (dtype == IPMC_F64)
-    hipLaunchKernelGGL(normal_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, seed,
-                       chain_offset, n_chains, step, k, (double*)out);
-  else
-    hipLaunchKernelGGL(normal_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, seed,
-                       chain_offset, n_chains, step, k, (float*)out);
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(normal_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, seed, chain_offset,
+                       n_chains, step, k, (T*)out);
+  });
   return check_launch("normal_kernel");
 }
 
@@ -613,13 +587,11 @@ int ipmc_pcn_draws(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64
   if (n_chains > INT64_MAX / k / n_steps) return fail(IPMC_ERR_INVALID, "n_steps * n_chains * k overflows");
   const int64_t total = n_steps * n_chains * k;
   const int64_t blocks = std::min<int64_t>((total + 255) / 256, 65536);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == IPMC_F64)
-    hipLaunchKernelGGL(draws_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st, seed, chain_offset, n_chains,
-                       step0, total, k, (const double*)prior_sqrt, (const double*)prior_chol, (double*)w, log_r);
-  else
-    hipLaunchKernelGGL(draws_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, seed, chain_offset, n_chains,
-                       step0, total, k, (const float*)prior_sqrt, (const float*)prior_chol, (float*)w, log_r);
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(draws_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, seed, chain_offset,
+                       n_chains, step0, total, k, (const T*)prior_sqrt, (const T*)prior_chol, (T*)w, log_r);
+  });
   return check_launch("draws_kernel");
 }
 

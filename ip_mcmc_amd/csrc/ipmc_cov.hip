@@ -372,41 +372,23 @@ extern "C" int ipmc_scatter(const void* x, int32_t dtype, int64_t n_chains, int6
   const dim3 grid((unsigned)groups), block((unsigned)threads);
   hipError_t attr = hipSuccess;
   // more than 64 KiB of dynamic LDS has to be allowed per kernel
-#define IPMC_COV(T, N, E, PAIR, DS)                                                                              \
-  do {                                                                                                           \
-    auto kern = scatter_kernel<T, N, E, PAIR, DS>;                                                               \
-    if (lds > 65536) attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (attr == hipSuccess)                                                                                      \
-      hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)x, center, a, scatter_out, dsum_out);            \
-  } while (0)
-#define IPMC_COV_D(T, N, E, PAIR) \
-  do {                            \
-    if (dsum_out)                 \
-      IPMC_COV(T, N, E, PAIR, true);  \
-    else                          \
-      IPMC_COV(T, N, E, PAIR, false); \
-  } while (0)
-#define IPMC_COV_T(T)                            \
-  do {                                           \
-    if (threads == kCovThreads) {                \
-      if (pairs)                                 \
-        IPMC_COV_D(T, kCovThreads, 4, true);     \
-      else                                       \
-        IPMC_COV_D(T, kCovThreads, 6, false);    \
-    } else {                                     \
-      if (pairs)                                 \
-        IPMC_COV_D(T, 256, 8, true);             \
-      else                                       \
-        IPMC_COV_D(T, 256, 8, false);            \
-    }                                            \
-  } while (0)
-  if (dtype == IPMC_F64)
-    IPMC_COV_T(double);
-  else
-    IPMC_COV_T(float);
-#undef IPMC_COV_T
-#undef IPMC_COV_D
-#undef IPMC_COV
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    with_bool(threads == kCovThreads, [&](auto wide) {
+      with_bool(pairs, [&](auto pair) {
+        with_bool(dsum_out != nullptr, [&](auto ds) {
+          constexpr bool kWide = decltype(wide)::value, kPair = decltype(pair)::value;
+          // threads and loads per lane and tile: per_lane above
+          auto kern = scatter_kernel<T, kWide ? kCovThreads : 256, !kWide ? 8 : (kPair ? 4 : 6), kPair,
+                                     decltype(ds)::value>;
+          if (lds > 65536)
+            attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+          if (attr == hipSuccess)
+            hipLaunchKernelGGL(kern, grid, block, lds, st, (const T*)x, center, a, scatter_out, dsum_out);
+        });
+      });
+    });
+  });
   if (attr != hipSuccess) {
     set_error("%s: %s", fn, hipGetErrorString(attr));
     return IPMC_ERR_DEVICE;

@@ -1,5 +1,21 @@
-// Chain diagnostics on the device: batched normalised autocorrelation.
-//
+// Chain diagnostics on the device, everything in fp64 on load:
+//   autocorrelation   ipmc_autocorr: batched normalised autocorrelation of series;
+//   burn-in           ipmc_burn_in: len_burn_in for a batch of chains;
+//   ordered sums      ipmc_ordered_sum, ipmc_block_sums, ipmc_centered_sq_block_sums:
+//                     column sums in a fixed row order (the posterior mean and the
+//                     variance across chains);
+//   convergence       ipmc_split_stats, ipmc_mean_acov, ipmc_moments_stats: the
+//                     per-chain parts of split-R-hat / ESS / MCSE.
+// The kernels come first, grouped in that order, then the entry points.  The lag
+// sum r(tau) = sum_i xs[i] xs[i + tau] of the autocorrelation and of the
+// convergence kernels is one body per access pattern (lag_sum_staged,
+// lag_sum_streamed), so the paths chosen by the series length add the same
+// products in the same order.
+#include "ipmc_internal.hpp"
+
+namespace ipmc {
+
+// ---------------------------------------------------------- autocorrelation
 // For every series x (one chain's samples of one component, or one window of
 // it) this computes what MCMCSampler.autocorr does for one series
 // (sampler.py:43-54): x_ = x - mean(x), r[tau] = sum_t x_[t] x_[t+tau]
@@ -12,84 +28,20 @@
 // tau = tid, tid + 256, ... with the inner sum over t read from LDS.  Longer
 // series (> kAcMaxLen samples) stream through LDS tiles instead
 // (autocorr_long_kernel), with the same summation order.
-#include "ipmc_internal.hpp"
-
-namespace ipmc {
-
-constexpr int kAcBlock = 256;
+constexpr int kDiagBlock = 256;  // lanes of every workgroup of the lag sums and of the convergence kernels
 constexpr int kAcMaxLen = 8192;  // doubles staged per series (64 KiB LDS)
+constexpr int kAcTile = 2048;    // samples per streamed tile
+// products formed per batch before they are added in order: a lone wave's
+// dependent add would otherwise wait out an LDS latency per term (measured:
+// ~120 cycles per term without it)
+constexpr int kCvBatch = 16;
 
-template <typename T>
-__global__ __launch_bounds__(kAcBlock) void autocorr_kernel(const T* __restrict__ x, int64_t n_series, int64_t len,
-                                                             int64_t stride_series, int64_t stride_t, int max_lag,
-                                                             double* __restrict__ out) {
-  __shared__ double xs[kAcMaxLen];
-  __shared__ double red[kAcBlock];
-  const int64_t s = blockIdx.x;
-  if (s >= n_series) return;
-  const T* src = x + s * stride_series;
-  double part = 0.0;
-  for (int64_t t = threadIdx.x; t < len; t += kAcBlock) {
-    const double v = (double)src[t * stride_t];
-    xs[t] = v;
-    part += v;
-  }
+// The block's partials, one per thread, added by a tree (128, 64, ..., 1);
+// every thread gets the sum, and red is free again on return.
+__device__ inline double block_tree_sum(double part, double* red) {
   red[threadIdx.x] = part;
   __syncthreads();
-  for (int off = kAcBlock / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  const double mean = red[0] / (double)len;
-  __syncthreads();
-  for (int64_t t = threadIdx.x; t < len; t += kAcBlock) xs[t] = xs[t] - mean;
-  __syncthreads();
-  // r[0] first (every thread needs it for the normalisation)
-  double r0p = 0.0;
-  for (int64_t t = threadIdx.x; t < len; t += kAcBlock) r0p += xs[t] * xs[t];
-  red[threadIdx.x] = r0p;
-  __syncthreads();
-  for (int off = kAcBlock / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  const double r0 = red[0];
-  double* o = out + s * max_lag;
-  for (int tau = threadIdx.x; tau < max_lag; tau += kAcBlock) {
-    if (r0 == 0.0) {
-      o[tau] = 1.0;
-      continue;
-    }
-    double r = 0.0;
-    for (int64_t t = 0; t + tau < len; ++t) r += xs[t] * xs[t + tau];
-    o[tau] = r / r0;
-  }
-}
-
-// Series longer than kAcMaxLen: the same sums from global memory.  A block
-// owns kAcBlock consecutive lags of one series (grid: series x lag tiles),
-// recomputes the mean and r[0] with the short kernel's strided-partials + tree
-// order, and streams the series through LDS in tiles of kAcTile samples:
-// a = x_[t0 .. t0+kAcTile), b = x_[t0+tau0 .. t0+tau0+kAcTile+kAcBlock).
-// Each thread's r[tau] is still the ascending sum over t, so the results equal
-// the short kernel's bit for bit.
-constexpr int kAcTile = 2048;
-
-template <typename T>
-__device__ double ac_block_sum(const T* src, int64_t len, int64_t stride_t, double sub, bool square, double* red) {
-  double part = 0.0;
-  for (int64_t t = threadIdx.x; t < len; t += kAcBlock) {
-    const double v = (double)src[t * stride_t];
-    if (square) {
-      const double c = v - sub;
-      part += c * c;
-    } else {
-      part += v;
-    }
-  }
-  red[threadIdx.x] = part;
-  __syncthreads();
-  for (int off = kAcBlock / 2; off > 0; off >>= 1) {
+  for (int off = kDiagBlock / 2; off > 0; off >>= 1) {
     if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
     __syncthreads();
   }
@@ -98,45 +50,122 @@ __device__ double ac_block_sum(const T* src, int64_t len, int64_t stride_t, doub
   return r;
 }
 
+// r(tau) = sum of xs[i] * xs[i + tau] over i + tau < n, ascending in i, of a
+// centred series staged in LDS.
+__device__ inline double lag_sum_staged(const double* xs, int n, int tau) {
+  double r = 0.0;
+  int i = 0;
+  for (; i + kCvBatch + tau <= n; i += kCvBatch) {  // the reads of a batch in flight together
+    double p[kCvBatch];
+#pragma unroll
+    for (int u = 0; u < kCvBatch; ++u) p[u] = xs[i + u] * xs[i + u + tau];
+#pragma unroll
+    for (int u = 0; u < kCvBatch; ++u) r = r + p[u];  // added in ascending i all the same
+  }
+  for (; i + tau < n; ++i) r = r + xs[i] * xs[i + tau];
+  return r;
+}
+
+// The same sum for the lag tau0 + threadIdx.x of a series of len > kAcMaxLen
+// samples in global memory, xs = src - sub.  The block owns the kDiagBlock
+// consecutive lags from tau0 and streams the series through LDS in tiles of
+// kAcTile samples: a = xs[t0 .. t0+kAcTile), b = xs[t0+tau0 .. t0+tau0+kAcTile+kDiagBlock).
+// Each thread's r(tau) is still the ascending sum over i, so the bits equal
+// lag_sum_staged's.  Every thread of the block calls this (barriers); one with
+// no lag to compute passes active = false.
 template <typename T>
-__global__ __launch_bounds__(kAcBlock) void autocorr_long_kernel(const T* __restrict__ x, int64_t n_series,
-                                                                  int64_t len, int64_t stride_series,
-                                                                  int64_t stride_t, int max_lag,
-                                                                  double* __restrict__ out) {
-  __shared__ double a[kAcTile];
-  __shared__ double b[kAcTile + kAcBlock];
-  __shared__ double red[kAcBlock];
+__device__ inline double lag_sum_streamed(const T* src, int64_t stride_t, int64_t len, double sub, int tau0,
+                                          bool active, double* a, double* b) {
+  const int sh = (int)threadIdx.x;
+  const int tau = tau0 + sh;
+  double r = 0.0;
+  for (int64_t t0 = 0; t0 + tau0 < len; t0 += kAcTile) {
+    for (int i = sh; i < kAcTile; i += kDiagBlock) {
+      const int64_t t = t0 + i;
+      a[i] = t < len ? (double)src[t * stride_t] - sub : 0.0;
+    }
+    for (int i = sh; i < kAcTile + kDiagBlock; i += kDiagBlock) {
+      const int64_t t = t0 + tau0 + i;
+      b[i] = t < len ? (double)src[t * stride_t] - sub : 0.0;
+    }
+    __syncthreads();
+    if (active) {
+      const int64_t rem = len - tau - t0;  // terms t0 + i with t0 + i + tau < len
+      const int n = rem < kAcTile ? (int)(rem > 0 ? rem : 0) : kAcTile;
+      int i = 0;
+      for (; i + kCvBatch <= n; i += kCvBatch) {
+        double p[kCvBatch];
+#pragma unroll
+        for (int u = 0; u < kCvBatch; ++u) p[u] = a[i + u] * b[i + u + sh];
+#pragma unroll
+        for (int u = 0; u < kCvBatch; ++u) r = r + p[u];
+      }
+      for (; i < n; ++i) r = r + a[i] * b[i + sh];
+    }
+    __syncthreads();
+  }
+  return r;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kDiagBlock) void autocorr_kernel(const T* __restrict__ x, int64_t n_series, int64_t len,
+                                                               int64_t stride_series, int64_t stride_t, int max_lag,
+                                                               double* __restrict__ out) {
+  __shared__ double xs[kAcMaxLen];
+  __shared__ double red[kDiagBlock];
   const int64_t s = blockIdx.x;
-  const int tau0 = blockIdx.y * kAcBlock;
+  if (s >= n_series) return;
+  const T* src = x + s * stride_series;
+  double part = 0.0;
+  for (int64_t t = threadIdx.x; t < len; t += kDiagBlock) {
+    const double v = (double)src[t * stride_t];
+    xs[t] = v;
+    part += v;
+  }
+  const double mean = block_tree_sum(part, red) / (double)len;
+  for (int64_t t = threadIdx.x; t < len; t += kDiagBlock) xs[t] = xs[t] - mean;
+  __syncthreads();
+  // r[0] first (every thread needs it for the normalisation)
+  double r0p = 0.0;
+  for (int64_t t = threadIdx.x; t < len; t += kDiagBlock) r0p += xs[t] * xs[t];
+  const double r0 = block_tree_sum(r0p, red);
+  double* o = out + s * max_lag;
+  for (int tau = threadIdx.x; tau < max_lag; tau += kDiagBlock)
+    o[tau] = r0 == 0.0 ? 1.0 : lag_sum_staged(xs, (int)len, tau) / r0;
+}
+
+// Series longer than kAcMaxLen: the same sums from global memory.  A block
+// owns kDiagBlock consecutive lags of one series (grid: series x lag tiles) and
+// recomputes the mean and r[0] with the short kernel's strided-partials + tree
+// order, so the results equal the short kernel's bit for bit.
+template <typename T>
+__global__ __launch_bounds__(kDiagBlock) void autocorr_long_kernel(const T* __restrict__ x, int64_t n_series,
+                                                                    int64_t len, int64_t stride_series,
+                                                                    int64_t stride_t, int max_lag,
+                                                                    double* __restrict__ out) {
+  __shared__ double a[kAcTile];
+  __shared__ double b[kAcTile + kDiagBlock];
+  __shared__ double red[kDiagBlock];
+  const int64_t s = blockIdx.x;
+  const int tau0 = blockIdx.y * kDiagBlock;
   if (s >= n_series || tau0 >= max_lag) return;
   const T* src = x + s * stride_series;
-  const double mean = ac_block_sum(src, len, stride_t, 0.0, false, red) / (double)len;
-  const double r0 = ac_block_sum(src, len, stride_t, mean, true, red);
+  double part = 0.0;
+  for (int64_t t = threadIdx.x; t < len; t += kDiagBlock) part += (double)src[t * stride_t];
+  const double mean = block_tree_sum(part, red) / (double)len;
+  part = 0.0;
+  for (int64_t t = threadIdx.x; t < len; t += kDiagBlock) {
+    const double c = (double)src[t * stride_t] - mean;
+    part += c * c;
+  }
+  const double r0 = block_tree_sum(part, red);
   const int tau = tau0 + (int)threadIdx.x;
   double* o = out + s * max_lag;
   if (r0 == 0.0) {
     if (tau < max_lag) o[tau] = 1.0;
     return;
   }
-  double r = 0.0;
-  for (int64_t t0 = 0; t0 + tau0 < len; t0 += kAcTile) {
-    for (int i = threadIdx.x; i < kAcTile; i += kAcBlock) {
-      const int64_t t = t0 + i;
-      a[i] = t < len ? (double)src[t * stride_t] - mean : 0.0;
-    }
-    for (int i = threadIdx.x; i < kAcTile + kAcBlock; i += kAcBlock) {
-      const int64_t t = t0 + tau0 + i;
-      b[i] = t < len ? (double)src[t * stride_t] - mean : 0.0;
-    }
-    __syncthreads();
-    if (tau < max_lag) {
-      const int64_t rem = len - tau - t0;  // terms t0 + i with t0 + i + tau < len
-      const int n = rem < kAcTile ? (int)(rem > 0 ? rem : 0) : kAcTile;
-      const int sh = (int)threadIdx.x;
-      for (int i = 0; i < n; ++i) r += a[i] * b[i + sh];
-    }
-    __syncthreads();
-  }
+  const double r = lag_sum_streamed(src, stride_t, len, mean, tau0, tau < max_lag, a, b);
   if (tau < max_lag) o[tau] = r / r0;
 }
 
@@ -259,6 +288,7 @@ __global__ void burn_in_search_kernel(int64_t n_chains, int64_t len, int w, cons
   out[c] = res;
 }
 
+// ------------------------------------------------------------ ordered sums
 // The chain-ordered column sums behind the many-chain posterior mean
 // (shard.ordered_sum_sharded): acc[j] = (((acc[j] + x_0j/div) + x_1j/div) + ...)
 // strictly in row order, the additions of ipmc_host_ordered_sum (same IEEE
@@ -344,11 +374,16 @@ __global__ __launch_bounds__(kOsBlock) void ordered_sum_kernel(const double* __r
 // kBsUnroll rows ahead of its adds; a block's B dependent adds are the critical
 // path (B = 1 024: tens of microseconds for any number of blocks that fits the
 // chip), where a whole-column chain over 65 536 rows takes ~0.7 ms.
+// The term added per row is x, x / div, or (x - center[j])^2: the centred
+// second stage of a two-pass variance across chains, in the same fixed order.
 constexpr int kBsThreads = 256;
 constexpr int kBsUnroll = 16;
+enum BsTerm { kBsPlain, kBsDiv, kBsCenteredSq };
 
+template <BsTerm kTerm>
 __global__ __launch_bounds__(kBsThreads) void block_sums_kernel(const double* __restrict__ x, int64_t n_rows, int64_t k,
                                                                int64_t stride, int64_t B, double div,
+                                                               const double* __restrict__ center,
                                                                double* __restrict__ out) {
   const int64_t t = (int64_t)blockIdx.x * kBsThreads + threadIdx.x;
   const int64_t nb = (n_rows + B - 1) / B;
@@ -357,147 +392,28 @@ __global__ __launch_bounds__(kBsThreads) void block_sums_kernel(const double* __
   const int64_t r0 = b * B;
   const int64_t rows = (n_rows - r0) < B ? (n_rows - r0) : B;
   const double* p = x + r0 * stride + j;
+  const double c = kTerm == kBsCenteredSq ? center[j] : 0.0;
+  auto term = [&](double v) {
+    if constexpr (kTerm == kBsCenteredSq) {
+      const double d = v - c;
+      return d * d;
+    } else if constexpr (kTerm == kBsDiv) {
+      return v / div;
+    } else {
+      return v;
+    }
+  };
   double s = 0.0;
   int64_t r = 0;
   for (; r + kBsUnroll <= rows; r += kBsUnroll) {
     double v[kBsUnroll];
 #pragma unroll
     for (int u = 0; u < kBsUnroll; ++u) v[u] = p[(r + u) * stride];
-    if (div == 1.0) {
 #pragma unroll
-      for (int u = 0; u < kBsUnroll; ++u) s = s + v[u];
-    } else {
-#pragma unroll
-      for (int u = 0; u < kBsUnroll; ++u) s = s + v[u] / div;
-    }
+    for (int u = 0; u < kBsUnroll; ++u) s = s + term(v[u]);
   }
-  for (; r < rows; ++r) s = div == 1.0 ? s + p[r * stride] : s + p[r * stride] / div;
+  for (; r < rows; ++r) s = s + term(p[r * stride]);
   out[b * k + j] = s;
-}
-
-}  // namespace ipmc
-
-using namespace ipmc;
-
-extern "C" int ipmc_ordered_sum(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride, double div,
-                                double* acc, void* stream) {
-  if (n_rows < 0 || k < 0 || row_stride < k) {
-    set_error("ipmc_ordered_sum: bad shape (n_rows, k >= 0, row_stride >= k)");
-    return IPMC_ERR_INVALID;
-  }
-  if (n_rows == 0 || k == 0) return IPMC_OK;
-  if (!rows || !acc) {
-    set_error("ipmc_ordered_sum: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
-  hipLaunchKernelGGL(ordered_sum_kernel, dim3((unsigned)((k + kOsCols - 1) / kOsCols)), dim3(kOsBlock), 0,
-                     (hipStream_t)stream, rows, n_rows, k, row_stride, div, acc);
-  return check_launch("ordered_sum_kernel");
-}
-
-extern "C" int ipmc_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride, int64_t block_rows,
-                               double div, double* out, void* stream) {
-  if (n_rows < 0 || k < 0 || row_stride < k || block_rows <= 0) {
-    set_error("ipmc_block_sums: bad shape (n_rows, k >= 0, row_stride >= k, block_rows > 0)");
-    return IPMC_ERR_INVALID;
-  }
-  if (n_rows == 0 || k == 0) return IPMC_OK;
-  if (!rows || !out) {
-    set_error("ipmc_block_sums: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
-  const int64_t lanes = (n_rows + block_rows - 1) / block_rows * k;
-  hipLaunchKernelGGL(block_sums_kernel, dim3((unsigned)((lanes + kBsThreads - 1) / kBsThreads)), dim3(kBsThreads), 0,
-                     (hipStream_t)stream, rows, n_rows, k, row_stride, block_rows, div, out);
-  return check_launch("block_sums_kernel");
-}
-
-extern "C" int ipmc_burn_in(const void* x, int32_t dtype, int64_t n_chains, int32_t n_vars, int64_t len,
-                            int64_t stride_chain, int64_t stride_var, int64_t stride_t, int32_t window,
-                            double threshold, uint32_t* flags_scratch, int64_t* out, void* stream) {
-  if (n_chains < 0 || n_vars <= 0 || len < 0 || window <= 0) {
-    set_error("ipmc_burn_in: bad sizes (n_vars and window must be positive)");
-    return IPMC_ERR_INVALID;
-  }
-  if (n_chains == 0) return IPMC_OK;
-  if (len < window) {
-    set_error("ipmc_burn_in: series of %lld samples shorter than the window %d", (long long)len, window);
-    return IPMC_ERR_INVALID;
-  }
-  if (!x || !out || !flags_scratch) {
-    set_error("ipmc_burn_in: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
-  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
-    set_error("ipmc_burn_in: bad dtype");
-    return IPMC_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t words = (len + 31) / 32;
-  if (hipMemsetAsync(flags_scratch, 0, (size_t)(n_chains * words) * sizeof(uint32_t), st) != hipSuccess) {
-    set_error("ipmc_burn_in: memset failed");
-    return IPMC_ERR_DEVICE;
-  }
-  const int64_t ns = n_chains * n_vars;
-  const unsigned nb = (unsigned)((ns + 255) / 256);
-  if (dtype == IPMC_F64)
-    hipLaunchKernelGGL(burn_in_flags_kernel<double>, dim3(nb), dim3(256), 0, st, (const double*)x, n_chains, n_vars,
-                       len, stride_chain, stride_var, stride_t, window, threshold, (unsigned*)flags_scratch, words);
-  else
-    hipLaunchKernelGGL(burn_in_flags_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)x, n_chains, n_vars,
-                       len, stride_chain, stride_var, stride_t, window, threshold, (unsigned*)flags_scratch, words);
-  int rc = check_launch("burn_in_flags_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL(burn_in_search_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, st, n_chains, len,
-                     window, (const unsigned*)flags_scratch, words, out);
-  return check_launch("burn_in_search_kernel");
-}
-
-extern "C" int ipmc_autocorr(const void* x, int32_t dtype, int64_t n_series, int64_t len, int64_t stride_series,
-                             int64_t stride_t, int32_t max_lag, double* out, void* stream) {
-  if (n_series < 0 || len < 0 || max_lag < 0) {
-    set_error("ipmc_autocorr: negative size");
-    return IPMC_ERR_INVALID;
-  }
-  if (n_series == 0 || max_lag == 0) return IPMC_OK;
-  if (len == 0 || !x || !out) {
-    set_error("ipmc_autocorr: empty series or NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
-  if (max_lag > len) {
-    set_error("ipmc_autocorr: max_lag %d exceeds the series length %lld", max_lag, (long long)len);
-    return IPMC_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (len > kAcMaxLen) {
-    if (n_series > 0x7fffffff) {
-      set_error("ipmc_autocorr: at most 2^31 - 1 long series per call");
-      return IPMC_ERR_INVALID;
-    }
-    const dim3 grid((unsigned)n_series, (unsigned)((max_lag + kAcBlock - 1) / kAcBlock));
-    if (dtype == IPMC_F64)
-      hipLaunchKernelGGL(autocorr_long_kernel<double>, grid, dim3(kAcBlock), 0, st, (const double*)x, n_series, len,
-                         stride_series, stride_t, max_lag, out);
-    else if (dtype == IPMC_F32)
-      hipLaunchKernelGGL(autocorr_long_kernel<float>, grid, dim3(kAcBlock), 0, st, (const float*)x, n_series, len,
-                         stride_series, stride_t, max_lag, out);
-    else {
-      set_error("ipmc_autocorr: bad dtype");
-      return IPMC_ERR_INVALID;
-    }
-    return check_launch("autocorr_long_kernel");
-  }
-  if (dtype == IPMC_F64)
-    hipLaunchKernelGGL(autocorr_kernel<double>, dim3((unsigned)n_series), dim3(kAcBlock), 0, st, (const double*)x,
-                       n_series, len, stride_series, stride_t, max_lag, out);
-  else if (dtype == IPMC_F32)
-    hipLaunchKernelGGL(autocorr_kernel<float>, dim3((unsigned)n_series), dim3(kAcBlock), 0, st, (const float*)x,
-                       n_series, len, stride_series, stride_t, max_lag, out);
-  else {
-    set_error("ipmc_autocorr: bad dtype");
-    return IPMC_ERR_INVALID;
-  }
-  return check_launch("autocorr_kernel");
 }
 
 // ------------------------------------------------- convergence across chains
@@ -520,14 +436,6 @@ extern "C" int ipmc_autocorr(const void* x, int32_t dtype, int64_t n_series, int
 // an ulp of a mean that is many spreads large, and both mappings (and the
 // host definition, in sample order) round the same value: Bn, the covariance
 // of such means, multiplies a change of a mean by 2 |mean| / spread.
-namespace ipmc {
-
-constexpr int kCvBlock = 256;
-// products formed per batch before they are added in order: a lone wave's
-// dependent add would otherwise wait out an LDS latency per term (measured:
-// ~120 cycles per term without it)
-constexpr int kCvBatch = 16;
-
 __host__ __device__ inline bool cv_lanes_over_time(int64_t N, int k, int64_t stride_t) {
   return N >= 32 && (stride_t == 1 || k < 16);
 }
@@ -545,11 +453,11 @@ __device__ inline double cv_wave_sum(double v) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(kCvBlock) void split_stats_vars_kernel(const T* __restrict__ x, int64_t n_chains,
+__global__ __launch_bounds__(kDiagBlock) void split_stats_vars_kernel(const T* __restrict__ x, int64_t n_chains,
                                                                    int64_t N, int k, int64_t s_chain, int64_t s_t,
                                                                    int64_t s_var, double* __restrict__ mean_out,
                                                                    double* __restrict__ var_out) {
-  const int64_t g = (int64_t)blockIdx.x * kCvBlock + threadIdx.x;
+  const int64_t g = (int64_t)blockIdx.x * kDiagBlock + threadIdx.x;
   if (g >= 2 * n_chains * k) return;
   const int64_t m = g / k;
   const int v = (int)(g - m * k);
@@ -570,12 +478,12 @@ __global__ __launch_bounds__(kCvBlock) void split_stats_vars_kernel(const T* __r
 }
 
 template <typename T>
-__global__ __launch_bounds__(kCvBlock) void split_stats_time_kernel(const T* __restrict__ x, int64_t n_chains,
+__global__ __launch_bounds__(kDiagBlock) void split_stats_time_kernel(const T* __restrict__ x, int64_t n_chains,
                                                                    int64_t N, int k, int64_t s_chain, int64_t s_t,
                                                                    int64_t s_var, double* __restrict__ mean_out,
                                                                    double* __restrict__ var_out) {
   const int lane = threadIdx.x & 63;
-  const int64_t g = (int64_t)blockIdx.x * (kCvBlock / 64) + (threadIdx.x >> 6);  // one series per wave
+  const int64_t g = (int64_t)blockIdx.x * (kDiagBlock / 64) + (threadIdx.x >> 6);  // one series per wave
   if (g >= 2 * n_chains * k) return;
   const int64_t m = g / k;
   const int v = (int)(g - m * k);
@@ -595,24 +503,23 @@ __global__ __launch_bounds__(kCvBlock) void split_stats_time_kernel(const T* __r
     var_out[g] = q / (double)(N - 1);
   }
 }
-
 // partial[b, tau, v] = sum over the split chains m of block b (block_chains
 // consecutive ones, from zero in m order) of gamma_m(tau) = r_m(tau) / N,
 // r_m(tau) = sum_i xs[i] xs[i + tau] ascending in i, xs = x - mean[m, v].
-// One workgroup per (b, v, tile of kCvBlock lags); a thread owns one lag and
+// One workgroup per (b, v, tile of kDiagBlock lags); a thread owns one lag and
 // keeps its running sum in a register while the block walks its split chains,
 // each series staged (centred) in LDS once: the (2C, k, L) per-chain lag sums
 // never exist.  The products are compute, not bandwidth (N loads feed N * L
 // multiply-adds), so the staging load's stride matters little here.
 template <typename T>
-__global__ __launch_bounds__(kCvBlock) void mean_acov_kernel(const T* __restrict__ x, int64_t n_chains, int64_t N,
-                                                            int k, int64_t s_chain, int64_t s_t, int64_t s_var,
-                                                            const double* __restrict__ mean, int max_lag,
-                                                            int64_t block_chains, double* __restrict__ partial) {
+__global__ __launch_bounds__(kDiagBlock) void mean_acov_kernel(const T* __restrict__ x, int64_t n_chains, int64_t N,
+                                                              int k, int64_t s_chain, int64_t s_t, int64_t s_var,
+                                                              const double* __restrict__ mean, int max_lag,
+                                                              int64_t block_chains, double* __restrict__ partial) {
   __shared__ double xs[kAcMaxLen];
   const int64_t b = blockIdx.x / k;
   const int v = (int)(blockIdx.x - b * k);
-  const int tau = (int)blockIdx.y * kCvBlock + (int)threadIdx.x;
+  const int tau = (int)blockIdx.y * kDiagBlock + (int)threadIdx.x;
   const int64_t m0 = b * block_chains;
   const int64_t m1 = (m0 + block_chains) < 2 * n_chains ? (m0 + block_chains) : 2 * n_chains;
   const int n = (int)N;
@@ -620,21 +527,9 @@ __global__ __launch_bounds__(kCvBlock) void mean_acov_kernel(const T* __restrict
   for (int64_t m = m0; m < m1; ++m) {
     const T* a = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
     const double mu = mean[m * k + v];
-    for (int t = threadIdx.x; t < n; t += kCvBlock) xs[t] = (double)a[t * s_t] - mu;
+    for (int t = threadIdx.x; t < n; t += kDiagBlock) xs[t] = (double)a[t * s_t] - mu;
     __syncthreads();
-    if (tau <= max_lag) {
-      double r = 0.0;
-      int i = 0;
-      for (; i + kCvBatch + tau <= n; i += kCvBatch) {  // the reads of a batch in flight together
-        double p[kCvBatch];
-#pragma unroll
-        for (int u = 0; u < kCvBatch; ++u) p[u] = xs[i + u] * xs[i + u + tau];
-#pragma unroll
-        for (int u = 0; u < kCvBatch; ++u) r = r + p[u];  // added in ascending i all the same
-      }
-      for (; i + tau < n; ++i) r = r + xs[i] * xs[i + tau];
-      acc = acc + r / (double)N;
-    }
+    if (tau <= max_lag) acc = acc + lag_sum_staged(xs, n, tau) / (double)N;
     __syncthreads();
   }
   if (tau <= max_lag) partial[(b * ((int64_t)max_lag + 1) + tau) * k + v] = acc;
@@ -649,12 +544,12 @@ __global__ __launch_bounds__(kCvBlock) void mean_acov_kernel(const T* __restrict
 constexpr int kCvDirectLen = 64;
 
 template <typename T>
-__global__ __launch_bounds__(kCvBlock) void mean_acov_direct_kernel(const T* __restrict__ x, int64_t n_chains,
-                                                                   int64_t N, int k, int64_t s_chain, int64_t s_t,
-                                                                   int64_t s_var, const double* __restrict__ mean,
-                                                                   int max_lag, int64_t block_chains,
-                                                                   int64_t n_blocks, double* __restrict__ partial) {
-  const int64_t g = (int64_t)blockIdx.x * kCvBlock + threadIdx.x;
+__global__ __launch_bounds__(kDiagBlock) void mean_acov_direct_kernel(const T* __restrict__ x, int64_t n_chains,
+                                                                     int64_t N, int k, int64_t s_chain, int64_t s_t,
+                                                                     int64_t s_var, const double* __restrict__ mean,
+                                                                     int max_lag, int64_t block_chains,
+                                                                     int64_t n_blocks, double* __restrict__ partial) {
+  const int64_t g = (int64_t)blockIdx.x * kDiagBlock + threadIdx.x;
   const int64_t per_block = ((int64_t)max_lag + 1) * k;
   if (g >= n_blocks * per_block) return;
   const int64_t b = g / per_block;
@@ -676,54 +571,25 @@ __global__ __launch_bounds__(kCvBlock) void mean_acov_direct_kernel(const T* __r
   partial[g] = acc;  // g == (b * (max_lag + 1) + tau) * k + v
 }
 
-// N > kAcMaxLen: the series streams through LDS in tiles as in
-// autocorr_long_kernel; every r_m(tau) is still the ascending sum over i, so
-// the bits equal the short kernel's.
+// N > kAcMaxLen: each split chain streams through LDS (lag_sum_streamed).
 template <typename T>
-__global__ __launch_bounds__(kCvBlock) void mean_acov_long_kernel(const T* __restrict__ x, int64_t n_chains,
-                                                                 int64_t N, int k, int64_t s_chain, int64_t s_t,
-                                                                 int64_t s_var, const double* __restrict__ mean,
-                                                                 int max_lag, int64_t block_chains,
-                                                                 double* __restrict__ partial) {
+__global__ __launch_bounds__(kDiagBlock) void mean_acov_long_kernel(const T* __restrict__ x, int64_t n_chains,
+                                                                   int64_t N, int k, int64_t s_chain, int64_t s_t,
+                                                                   int64_t s_var, const double* __restrict__ mean,
+                                                                   int max_lag, int64_t block_chains,
+                                                                   double* __restrict__ partial) {
   __shared__ double a[kAcTile];
-  __shared__ double bq[kAcTile + kCvBlock];
+  __shared__ double bq[kAcTile + kDiagBlock];
   const int64_t b = blockIdx.x / k;
   const int v = (int)(blockIdx.x - b * k);
-  const int tau0 = (int)blockIdx.y * kCvBlock;
-  const int sh = (int)threadIdx.x;
-  const int tau = tau0 + sh;
+  const int tau0 = (int)blockIdx.y * kDiagBlock;
+  const int tau = tau0 + (int)threadIdx.x;
   const int64_t m0 = b * block_chains;
   const int64_t m1 = (m0 + block_chains) < 2 * n_chains ? (m0 + block_chains) : 2 * n_chains;
   double acc = 0.0;
   for (int64_t m = m0; m < m1; ++m) {
     const T* src = cv_series(x, m, n_chains, N, s_chain, s_t) + v * s_var;
-    const double mu = mean[m * k + v];
-    double r = 0.0;
-    for (int64_t t0 = 0; t0 + tau0 < N; t0 += kAcTile) {
-      for (int i = threadIdx.x; i < kAcTile; i += kCvBlock) {
-        const int64_t t = t0 + i;
-        a[i] = t < N ? (double)src[t * s_t] - mu : 0.0;
-      }
-      for (int i = threadIdx.x; i < kAcTile + kCvBlock; i += kCvBlock) {
-        const int64_t t = t0 + tau0 + i;
-        bq[i] = t < N ? (double)src[t * s_t] - mu : 0.0;
-      }
-      __syncthreads();
-      if (tau <= max_lag) {
-        const int64_t rem = N - tau - t0;  // terms t0 + i with t0 + i + tau < N
-        const int n = rem < kAcTile ? (int)(rem > 0 ? rem : 0) : kAcTile;
-        int i = 0;
-        for (; i + kCvBatch <= n; i += kCvBatch) {
-          double p[kCvBatch];
-#pragma unroll
-          for (int u = 0; u < kCvBatch; ++u) p[u] = a[i + u] * bq[i + u + sh];
-#pragma unroll
-          for (int u = 0; u < kCvBatch; ++u) r = r + p[u];
-        }
-        for (; i < n; ++i) r = r + a[i] * bq[i + sh];
-      }
-      __syncthreads();
-    }
+    const double r = lag_sum_streamed(src, s_t, N, mean[m * k + v], tau0, tau <= max_lag, a, bq);
     if (tau <= max_lag) acc = acc + r / (double)N;
   }
   if (tau <= max_lag) partial[(b * ((int64_t)max_lag + 1) + tau) * k + v] = acc;
@@ -731,45 +597,15 @@ __global__ __launch_bounds__(kCvBlock) void mean_acov_long_kernel(const T* __res
 
 // keep="moments" sums -> per-chain mean and sample variance, the operations of
 // the host formula in its order: mean = s / n, var = (s2 - (s * s) / n) / (n - 1).
-__global__ __launch_bounds__(kCvBlock) void moments_stats_kernel(const double* __restrict__ sum_u,
-                                                                const double* __restrict__ sum_u2, int64_t count,
-                                                                double n, double* __restrict__ mean_out,
-                                                                double* __restrict__ var_out) {
-  const int64_t g = (int64_t)blockIdx.x * kCvBlock + threadIdx.x;
+__global__ __launch_bounds__(kDiagBlock) void moments_stats_kernel(const double* __restrict__ sum_u,
+                                                                  const double* __restrict__ sum_u2, int64_t count,
+                                                                  double n, double* __restrict__ mean_out,
+                                                                  double* __restrict__ var_out) {
+  const int64_t g = (int64_t)blockIdx.x * kDiagBlock + threadIdx.x;
   if (g >= count) return;
   const double s = sum_u[g];
   mean_out[g] = s / n;
   var_out[g] = (sum_u2[g] - (s * s) / n) / (n - 1.0);
-}
-
-// block_sums_kernel over (x - center[j])^2: the centred second stage of a
-// two-pass variance across chains, in the same fixed order.
-__global__ __launch_bounds__(kBsThreads) void centered_sq_block_sums_kernel(const double* __restrict__ x,
-                                                                           int64_t n_rows, int64_t k, int64_t stride,
-                                                                           const double* __restrict__ center,
-                                                                           int64_t B, double* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * kBsThreads + threadIdx.x;
-  const int64_t nb = (n_rows + B - 1) / B;
-  if (t >= nb * k) return;
-  const int64_t b = t / k, j = t - b * k;
-  const int64_t r0 = b * B;
-  const int64_t rows = (n_rows - r0) < B ? (n_rows - r0) : B;
-  const double* p = x + r0 * stride + j;
-  const double c = center[j];
-  double s = 0.0;
-  int64_t r = 0;
-  for (; r + kBsUnroll <= rows; r += kBsUnroll) {
-    double d[kBsUnroll];
-#pragma unroll
-    for (int u = 0; u < kBsUnroll; ++u) d[u] = p[(r + u) * stride] - c;
-#pragma unroll
-    for (int u = 0; u < kBsUnroll; ++u) s = s + d[u] * d[u];
-  }
-  for (; r < rows; ++r) {
-    const double d = p[r * stride] - c;
-    s = s + d * d;
-  }
-  out[b * k + j] = s;
 }
 
 // shared argument checks of ipmc_split_stats / ipmc_mean_acov; 0 = launch,
@@ -804,7 +640,132 @@ static int cv_check(const char* fn, const void* x, int32_t dtype, int64_t n_chai
   return 0;
 }
 
+// shared checks and launch of ipmc_block_sums / ipmc_centered_sq_block_sums
+static int block_sums(const char* fn, const double* rows, int64_t n_rows, int64_t k, int64_t row_stride,
+                      int64_t block_rows, double div, const double* center, bool centered, double* out,
+                      void* stream) {
+  if (n_rows < 0 || k < 0 || row_stride < k || block_rows <= 0) {
+    set_error("%s: bad shape (n_rows, k >= 0, row_stride >= k, block_rows > 0)", fn);
+    return IPMC_ERR_INVALID;
+  }
+  if (n_rows == 0 || k == 0) return IPMC_OK;
+  if (!rows || !out || (centered && !center)) {
+    set_error("%s: NULL pointer", fn);
+    return IPMC_ERR_INVALID;
+  }
+  const int64_t lanes = (n_rows + block_rows - 1) / block_rows * k;
+  // v / 1.0 == v: the term without the division gives the same bits sooner
+  auto kern = centered ? block_sums_kernel<kBsCenteredSq>
+                       : (div == 1.0 ? block_sums_kernel<kBsPlain> : block_sums_kernel<kBsDiv>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + kBsThreads - 1) / kBsThreads)), dim3(kBsThreads), 0,
+                     (hipStream_t)stream, rows, n_rows, k, row_stride, block_rows, div, center, out);
+  return check_launch(centered ? "centered_sq_block_sums_kernel" : "block_sums_kernel");
+}
+
 }  // namespace ipmc
+
+using namespace ipmc;
+
+extern "C" int ipmc_autocorr(const void* x, int32_t dtype, int64_t n_series, int64_t len, int64_t stride_series,
+                             int64_t stride_t, int32_t max_lag, double* out, void* stream) {
+  if (n_series < 0 || len < 0 || max_lag < 0) {
+    set_error("ipmc_autocorr: negative size");
+    return IPMC_ERR_INVALID;
+  }
+  if (n_series == 0 || max_lag == 0) return IPMC_OK;
+  if (len == 0 || !x || !out) {
+    set_error("ipmc_autocorr: empty series or NULL pointer");
+    return IPMC_ERR_INVALID;
+  }
+  if (max_lag > len) {
+    set_error("ipmc_autocorr: max_lag %d exceeds the series length %lld", max_lag, (long long)len);
+    return IPMC_ERR_INVALID;
+  }
+  const bool streamed = len > kAcMaxLen;
+  if (streamed && n_series > 0x7fffffff) {
+    set_error("ipmc_autocorr: at most 2^31 - 1 long series per call");
+    return IPMC_ERR_INVALID;
+  }
+  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
+    set_error("ipmc_autocorr: bad dtype");
+    return IPMC_ERR_INVALID;
+  }
+  const dim3 grid((unsigned)n_series, streamed ? (unsigned)((max_lag + kDiagBlock - 1) / kDiagBlock) : 1u);
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto kern = streamed ? autocorr_long_kernel<T> : autocorr_kernel<T>;
+    hipLaunchKernelGGL(kern, grid, dim3(kDiagBlock), 0, (hipStream_t)stream, (const T*)x, n_series, len, stride_series,
+                       stride_t, max_lag, out);
+  });
+  return check_launch(streamed ? "autocorr_long_kernel" : "autocorr_kernel");
+}
+
+extern "C" int ipmc_burn_in(const void* x, int32_t dtype, int64_t n_chains, int32_t n_vars, int64_t len,
+                            int64_t stride_chain, int64_t stride_var, int64_t stride_t, int32_t window,
+                            double threshold, uint32_t* flags_scratch, int64_t* out, void* stream) {
+  if (n_chains < 0 || n_vars <= 0 || len < 0 || window <= 0) {
+    set_error("ipmc_burn_in: bad sizes (n_vars and window must be positive)");
+    return IPMC_ERR_INVALID;
+  }
+  if (n_chains == 0) return IPMC_OK;
+  if (len < window) {
+    set_error("ipmc_burn_in: series of %lld samples shorter than the window %d", (long long)len, window);
+    return IPMC_ERR_INVALID;
+  }
+  if (!x || !out || !flags_scratch) {
+    set_error("ipmc_burn_in: NULL pointer");
+    return IPMC_ERR_INVALID;
+  }
+  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
+    set_error("ipmc_burn_in: bad dtype");
+    return IPMC_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t words = (len + 31) / 32;
+  if (hipMemsetAsync(flags_scratch, 0, (size_t)(n_chains * words) * sizeof(uint32_t), st) != hipSuccess) {
+    set_error("ipmc_burn_in: memset failed");
+    return IPMC_ERR_DEVICE;
+  }
+  const int64_t ns = n_chains * n_vars;
+  const unsigned nb = (unsigned)((ns + 255) / 256);
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(burn_in_flags_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)x, n_chains, n_vars, len,
+                       stride_chain, stride_var, stride_t, window, threshold, (unsigned*)flags_scratch, words);
+  });
+  int rc = check_launch("burn_in_flags_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(burn_in_search_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, st, n_chains, len,
+                     window, (const unsigned*)flags_scratch, words, out);
+  return check_launch("burn_in_search_kernel");
+}
+
+extern "C" int ipmc_ordered_sum(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride, double div,
+                                double* acc, void* stream) {
+  if (n_rows < 0 || k < 0 || row_stride < k) {
+    set_error("ipmc_ordered_sum: bad shape (n_rows, k >= 0, row_stride >= k)");
+    return IPMC_ERR_INVALID;
+  }
+  if (n_rows == 0 || k == 0) return IPMC_OK;
+  if (!rows || !acc) {
+    set_error("ipmc_ordered_sum: NULL pointer");
+    return IPMC_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(ordered_sum_kernel, dim3((unsigned)((k + kOsCols - 1) / kOsCols)), dim3(kOsBlock), 0,
+                     (hipStream_t)stream, rows, n_rows, k, row_stride, div, acc);
+  return check_launch("ordered_sum_kernel");
+}
+
+extern "C" int ipmc_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride, int64_t block_rows,
+                               double div, double* out, void* stream) {
+  return block_sums("ipmc_block_sums", rows, n_rows, k, row_stride, block_rows, div, nullptr, false, out, stream);
+}
+
+extern "C" int ipmc_centered_sq_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride,
+                                           const double* center, int64_t block_rows, double* out, void* stream) {
+  return block_sums("ipmc_centered_sq_block_sums", rows, n_rows, k, row_stride, block_rows, 1.0, center, true, out,
+                    stream);
+}
 
 extern "C" int ipmc_split_stats(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k,
                                 int64_t stride_chain, int64_t stride_t, int64_t stride_var, double* mean_out,
@@ -815,27 +776,17 @@ extern "C" int ipmc_split_stats(const void* x, int32_t dtype, int64_t n_chains, 
     set_error("ipmc_split_stats: NULL pointer");
     return IPMC_ERR_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
   const int64_t N = len / 2, series = 2 * n_chains * k;
   const bool over_time = cv_lanes_over_time(N, k, stride_t);
-  const int64_t per_block = over_time ? kCvBlock / 64 : kCvBlock;
-  const dim3 grid((unsigned)((series + per_block - 1) / per_block)), block(kCvBlock);
-#define IPMC_CV_STATS(KERNEL, T)                                                                              \
-  hipLaunchKernelGGL(KERNEL<T>, grid, block, 0, st, (const T*)x, n_chains, N, (int)k, stride_chain, stride_t, \
-                     stride_var, mean_out, var_out)
-  if (over_time) {
-    if (dtype == IPMC_F64)
-      IPMC_CV_STATS(split_stats_time_kernel, double);
-    else
-      IPMC_CV_STATS(split_stats_time_kernel, float);
-    return check_launch("split_stats_time_kernel");
-  }
-  if (dtype == IPMC_F64)
-    IPMC_CV_STATS(split_stats_vars_kernel, double);
-  else
-    IPMC_CV_STATS(split_stats_vars_kernel, float);
-#undef IPMC_CV_STATS
-  return check_launch("split_stats_vars_kernel");
+  const int64_t per_block = over_time ? kDiagBlock / 64 : kDiagBlock;
+  const dim3 grid((unsigned)((series + per_block - 1) / per_block));
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto kern = over_time ? split_stats_time_kernel<T> : split_stats_vars_kernel<T>;
+    hipLaunchKernelGGL(kern, grid, dim3(kDiagBlock), 0, (hipStream_t)stream, (const T*)x, n_chains, N, (int)k,
+                       stride_chain, stride_t, stride_var, mean_out, var_out);
+  });
+  return check_launch(over_time ? "split_stats_time_kernel" : "split_stats_vars_kernel");
 }
 
 extern "C" int ipmc_mean_acov(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k,
@@ -861,40 +812,28 @@ extern "C" int ipmc_mean_acov(const void* x, int32_t dtype, int64_t n_chains, in
     return IPMC_ERR_INVALID;
   }
   const int64_t n_blocks = (2 * n_chains + block_chains - 1) / block_chains;
-  const int64_t tiles = ((int64_t)max_lag + kCvBlock) / kCvBlock;  // ceil((max_lag + 1) / kCvBlock)
+  const int64_t tiles = ((int64_t)max_lag + kDiagBlock) / kDiagBlock;  // ceil((max_lag + 1) / kDiagBlock)
   if (tiles > 65535) {
     set_error("ipmc_mean_acov: max_lag %d needs more than 65535 lag tiles", max_lag);
     return IPMC_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(n_blocks * k), (unsigned)tiles), block(kCvBlock);
-#define IPMC_CV_ACOV(KERNEL, T)                                                                               \
-  hipLaunchKernelGGL(KERNEL<T>, grid, block, 0, st, (const T*)x, n_chains, N, (int)k, stride_chain, stride_t, \
-                     stride_var, mean, (int)max_lag, block_chains, partial_out)
-  if (N <= kCvDirectLen) {
-    const int64_t lanes = n_blocks * ((int64_t)max_lag + 1) * k;
-    const dim3 dgrid((unsigned)((lanes + kCvBlock - 1) / kCvBlock));
-    if (dtype == IPMC_F64)
-      hipLaunchKernelGGL(mean_acov_direct_kernel<double>, dgrid, block, 0, st, (const double*)x, n_chains, N, (int)k,
-                         stride_chain, stride_t, stride_var, mean, (int)max_lag, block_chains, n_blocks, partial_out);
-    else
-      hipLaunchKernelGGL(mean_acov_direct_kernel<float>, dgrid, block, 0, st, (const float*)x, n_chains, N, (int)k,
-                         stride_chain, stride_t, stride_var, mean, (int)max_lag, block_chains, n_blocks, partial_out);
-    return check_launch("mean_acov_direct_kernel");
-  }
-  if (N > kAcMaxLen) {
-    if (dtype == IPMC_F64)
-      IPMC_CV_ACOV(mean_acov_long_kernel, double);
-    else
-      IPMC_CV_ACOV(mean_acov_long_kernel, float);
-    return check_launch("mean_acov_long_kernel");
-  }
-  if (dtype == IPMC_F64)
-    IPMC_CV_ACOV(mean_acov_kernel, double);
-  else
-    IPMC_CV_ACOV(mean_acov_kernel, float);
-#undef IPMC_CV_ACOV
-  return check_launch("mean_acov_kernel");
+  const bool direct = N <= kCvDirectLen, streamed = N > kAcMaxLen;
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (direct) {
+      const int64_t lanes = n_blocks * ((int64_t)max_lag + 1) * k;
+      hipLaunchKernelGGL(mean_acov_direct_kernel<T>, dim3((unsigned)((lanes + kDiagBlock - 1) / kDiagBlock)),
+                         dim3(kDiagBlock), 0, st, (const T*)x, n_chains, N, (int)k, stride_chain, stride_t, stride_var,
+                         mean, (int)max_lag, block_chains, n_blocks, partial_out);
+    } else {
+      auto kern = streamed ? mean_acov_long_kernel<T> : mean_acov_kernel<T>;
+      hipLaunchKernelGGL(kern, dim3((unsigned)(n_blocks * k), (unsigned)tiles), dim3(kDiagBlock), 0, st, (const T*)x,
+                         n_chains, N, (int)k, stride_chain, stride_t, stride_var, mean, (int)max_lag, block_chains,
+                         partial_out);
+    }
+  });
+  return check_launch(direct ? "mean_acov_direct_kernel" : streamed ? "mean_acov_long_kernel" : "mean_acov_kernel");
 }
 
 extern "C" int ipmc_moments_stats(const double* sum_u, const double* sum_u2, int64_t n_chains, int32_t k, int64_t n,
@@ -913,28 +852,11 @@ extern "C" int ipmc_moments_stats(const double* sum_u, const double* sum_u2, int
     return IPMC_ERR_INVALID;
   }
   const int64_t count = n_chains * k;
-  if ((count + kCvBlock - 1) / kCvBlock > 0x7fffffff) {
+  if ((count + kDiagBlock - 1) / kDiagBlock > 0x7fffffff) {
     set_error("ipmc_moments_stats: too many values for one call");
     return IPMC_ERR_INVALID;
   }
-  hipLaunchKernelGGL(moments_stats_kernel, dim3((unsigned)((count + kCvBlock - 1) / kCvBlock)), dim3(kCvBlock), 0,
+  hipLaunchKernelGGL(moments_stats_kernel, dim3((unsigned)((count + kDiagBlock - 1) / kDiagBlock)), dim3(kDiagBlock), 0,
                      (hipStream_t)stream, sum_u, sum_u2, count, (double)n, mean_out, var_out);
   return check_launch("moments_stats_kernel");
-}
-
-extern "C" int ipmc_centered_sq_block_sums(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride,
-                                           const double* center, int64_t block_rows, double* out, void* stream) {
-  if (n_rows < 0 || k < 0 || row_stride < k || block_rows <= 0) {
-    set_error("ipmc_centered_sq_block_sums: bad shape (n_rows, k >= 0, row_stride >= k, block_rows > 0)");
-    return IPMC_ERR_INVALID;
-  }
-  if (n_rows == 0 || k == 0) return IPMC_OK;
-  if (!rows || !center || !out) {
-    set_error("ipmc_centered_sq_block_sums: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
-  const int64_t lanes = (n_rows + block_rows - 1) / block_rows * k;
-  hipLaunchKernelGGL(centered_sq_block_sums_kernel, dim3((unsigned)((lanes + kBsThreads - 1) / kBsThreads)),
-                     dim3(kBsThreads), 0, (hipStream_t)stream, rows, n_rows, k, row_stride, center, block_rows, out);
-  return check_launch("centered_sq_block_sums_kernel");
 }

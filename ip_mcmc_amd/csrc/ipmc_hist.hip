@@ -538,12 +538,11 @@ extern "C" int ipmc_minmax(const void* x, int32_t dtype, int64_t n_chains, int64
     span = (span + step - 1) / step * step;  // a multiple of k: a lane keeps its component in every workgroup
     n_groups = (total + span - 1) / span;
     const dim3 grid((unsigned)n_groups), block(kHsBlock);
-    if (dtype == IPMC_F64)
-      hipLaunchKernelGGL(minmax_inner_kernel<double>, grid, block, 0, st, (const double*)x, g, total, span, (int)k,
-                         step, pmin, pmax);
-    else
-      hipLaunchKernelGGL(minmax_inner_kernel<float>, grid, block, 0, st, (const float*)x, g, total, span, (int)k,
-                         step, pmin, pmax);
+    with_dtype(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(minmax_inner_kernel<T>, grid, block, 0, st, (const T*)x, g, total, span, (int)k, step, pmin,
+                         pmax);
+    });
     rc = check_launch("minmax_inner_kernel");
     if (rc) return rc;
   } else if (len > 0) {
@@ -554,12 +553,11 @@ extern "C" int ipmc_minmax(const void* x, int32_t dtype, int64_t n_chains, int64
     const int64_t uspan = (units + n_groups - 1) / n_groups;
     n_groups = (units + uspan - 1) / uspan;
     const dim3 grid((unsigned)n_groups), block(kHsBlock);
-    if (dtype == IPMC_F64)
-      hipLaunchKernelGGL(minmax_outer_kernel<double>, grid, block, 0, st, (const double*)x, g, units, uspan, nchunk,
-                         (int)k, pmin, pmax);
-    else
-      hipLaunchKernelGGL(minmax_outer_kernel<float>, grid, block, 0, st, (const float*)x, g, units, uspan, nchunk,
-                         (int)k, pmin, pmax);
+    with_dtype(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(minmax_outer_kernel<T>, grid, block, 0, st, (const T*)x, g, units, uspan, nchunk, (int)k, pmin,
+                         pmax);
+    });
     rc = check_launch("minmax_outer_kernel");
     if (rc) return rc;
   }
@@ -610,22 +608,14 @@ extern "C" int ipmc_hist1d(const void* x, int32_t dtype, int64_t n_chains, int64
     return IPMC_ERR_INVALID;
   }
   const dim3 grid((unsigned)n_groups, (unsigned)tiles), block(kHsBlock);
-#define IPMC_HS_1D(T, D)                                                                                       \
-  hipLaunchKernelGGL((hist1d_kernel<T, D>), grid, block, lds, st, (const T*)x, g, total, span, (int)k, (int)bins, \
-                     kt, copies_log2, edges, (unsigned long long*)counts, (unsigned long long*)below,            \
-                     (unsigned long long*)above)
-  if (dtype == IPMC_F64) {
-    if (g.dense)
-      IPMC_HS_1D(double, true);
-    else
-      IPMC_HS_1D(double, false);
-  } else {
-    if (g.dense)
-      IPMC_HS_1D(float, true);
-    else
-      IPMC_HS_1D(float, false);
-  }
-#undef IPMC_HS_1D
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    with_bool(g.dense, [&](auto dense) {
+      hipLaunchKernelGGL((hist1d_kernel<T, decltype(dense)::value>), grid, block, lds, st, (const T*)x, g, total, span,
+                         (int)k, (int)bins, kt, copies_log2, edges, (unsigned long long*)counts,
+                         (unsigned long long*)below, (unsigned long long*)above);
+    });
+  });
   return check_launch("hist1d_kernel");
 }
 
@@ -688,20 +678,12 @@ extern "C" int ipmc_histdd(const void* x, int32_t dtype, int64_t n_chains, int64
   const bool in_lds = n_cells <= kDdLdsCells && n_edges <= kDdLdsEdges;
   const size_t lds = in_lds ? sizeof(double) * n_edges + sizeof(uint32_t) * n_cells : 0;
   const dim3 grid((unsigned)n_groups), block(kHsBlock);
-#define IPMC_HS_DD(T, L)                                                                                      \
-  hipLaunchKernelGGL((histdd_kernel<T, L>), grid, block, lds, st, (const T*)x, g, total, span, ax, (int)n_cells, \
-                     n_edges, edges, (unsigned long long*)counts)
-  if (dtype == IPMC_F64) {
-    if (in_lds)
-      IPMC_HS_DD(double, true);
-    else
-      IPMC_HS_DD(double, false);
-  } else {
-    if (in_lds)
-      IPMC_HS_DD(float, true);
-    else
-      IPMC_HS_DD(float, false);
-  }
-#undef IPMC_HS_DD
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    with_bool(in_lds, [&](auto cells_in_lds) {
+      hipLaunchKernelGGL((histdd_kernel<T, decltype(cells_in_lds)::value>), grid, block, lds, st, (const T*)x, g, total,
+                         span, ax, (int)n_cells, n_edges, edges, (unsigned long long*)counts);
+    });
+  });
   return check_launch(in_lds ? "histdd_kernel (LDS cells)" : "histdd_kernel (global cells)");
 }

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/ipmc.h"
 
 namespace ipmc {
@@ -10,9 +12,24 @@ namespace ipmc {
 // lanes of one Lorenz-96 speculative chain when its slots span a whole block
 constexpr int kL96SpecBlockLanes = 256;
 
-
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+
+// Run-time value -> template argument at a launch site.  f is a generic lambda:
+//   with_dtype(dtype, [&](auto tag) { using T = decltype(tag); ... kernel<T> ... });
+//   with_bool(dense, [&](auto d) { ... kernel<T, decltype(d)::value> ... });
+// The caller has checked dtype (IPMC_F64 or IPMC_F32) where its order of checks says so.
+template <typename F>
+auto with_dtype(int32_t dtype, F&& f) {
+  if (dtype == IPMC_F64) return f(double{});
+  return f(float{});
+}
+
+template <typename F>
+auto with_bool(bool b, F&& f) {
+  if (b) return f(std::true_type{});
+  return f(std::false_type{});
+}
 
 // Lorenz-96 dispatch (ipmc_l96_f{32,64}.hip; REFERENCE arith in ipmc_l96_f{32,64}_ref.hip).
 // Returns IPMC_ERR_UNSUPPORTED when (D, lpc) has no instantiation.

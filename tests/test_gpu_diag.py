@@ -1,4 +1,5 @@
-"""Device chain diagnostics (ipmc_autocorr, ipmc_burn_in) vs the reference's outputs and the oracle."""
+"""Device chain diagnostics (ipmc_autocorr, ipmc_burn_in) vs the reference's outputs and the oracle, and the
+lag sums' length-selected kernels (ipmc_autocorr, ipmc_mean_acov) against one another, bit for bit."""
 import numpy as np
 import pytest
 
@@ -74,6 +75,52 @@ def test_autocorrelation_windows_and_chain_layout(orc):
     got = chain_autocorr(samples, 10)
     assert got.shape == (4, 5, 10)
     np.testing.assert_allclose(got[2, 3], orc.autocorr_ref(samples[2, :, 3])[:10], rtol=1e-10, atol=1e-12)
+
+
+# ------------------------------- the length-selected paths give the same bits
+def _mean_acov_times_n(data, N, max_lag):
+    """N * ipmc_mean_acov's partial for 4 split chains (C = 2, k = 2, block_chains = 1, the means given as
+    exactly 8.0): data (4, R, 2) are the split chains' samples, each padded with exactly 8.0 up to N."""
+    from ip_mcmc_amd import device as dev
+    from ip_mcmc_amd._lib import call
+
+    C, k, R = 2, 2, data.shape[1]
+    x = np.full((C, 2 * N, k), 8.0)
+    x[:, :R] = data[:C]  # split chain m < C is x[m, :N], m >= C is x[m - C, N:]
+    x[:, N:N + R] = data[C:]
+    t = torch.as_tensor(x).cuda()
+    mean = torch.full((2 * C, k), 8.0, dtype=torch.float64, device=t.device)
+    partial = torch.empty((2 * C, (max_lag + 1) * k), dtype=torch.float64, device=t.device)
+    call("ipmc_mean_acov", t.data_ptr(), dev.abi_dtype(t.dtype), C, 2 * N, k, 2 * N * k, k, 1, mean.data_ptr(),
+         max_lag, 1, partial.data_ptr(), dev.stream_handle(t.device))
+    return partial.cpu().numpy().reshape(2 * C, max_lag + 1, k) * N  # N a power of two: an exact scaling
+
+
+@pytest.mark.parametrize("R,N_a,N_b,max_lag", [(64, 64, 128, 63),  # factors read in place / staged in LDS
+                                               (512, 512, 16384, 300)])  # staged / streamed, two lag tiles
+def test_mean_acov_paths_give_the_same_bits(R, N_a, N_b, max_lag):
+    """The centred padding is exactly 0 and adds nothing to an ascending sum, so the kernel chosen by N
+    (N <= 64, N <= 8192, longer) must give the same r(tau) bit for bit."""
+    data = 8.0 + 0.01 * np.random.default_rng(41).normal(size=(4, R, 2))
+    a, b = _mean_acov_times_n(data, N_a, max_lag), _mean_acov_times_n(data, N_b, max_lag)
+    assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
+    assert len(np.unique(a[0, :, 0])) > max_lag // 2  # not one value at every lag (all zeros)
+
+
+def test_autocorr_short_and_long_kernel_give_the_same_bits():
+    """x[t + 256] = -x[t] makes every thread's strided partial of the mean exactly 0 in both kernels, so
+    xs = x; zero padding past 8 192 samples selects the streaming kernel and adds only zeros.  The products
+    are inexact: equal bits mean the same order of additions."""
+    from ip_mcmc_amd.diagnostics import autocorr
+
+    x = np.random.default_rng(42).normal(size=1024)
+    x[256:512] = -x[:256]
+    x[768:] = -x[512:768]
+    padded = np.zeros(9216)
+    padded[:1024] = x
+    short, long_ = autocorr(x, max_lag=600), autocorr(padded, max_lag=600)
+    assert np.array_equal(short.view(np.uint64), long_.view(np.uint64))
+    assert len(np.unique(short)) > 300  # not one value at every lag
 
 
 # ------------------------------------------------------ burn-in (§8(f) #2)
