@@ -36,6 +36,9 @@
  *                                                             ipmc_split_stats, ipmc_mean_acov,
  *                                                             ipmc_moments_stats, ipmc_centered_sq_block_sums
  *                                                             (split-R-hat, ESS and MCSE over the ensemble)
+ *   (nothing: the reference runs one chain)                   ipmc_sort_workspace, ipmc_pooled_sort, ipmc_rank_scores
+ *                                                             (rank-normalised split-R-hat, bulk / tail ESS and
+ *                                                             exact pooled quantiles from one sort on the device)
  *   wasserstein_distance's inputs     helpers.py:57-77,       ipmc_minmax, ipmc_hist1d, ipmc_histdd
  *   (intervals from the data's min    burgers_wasserstein_    (support, marginal and joint np.histogramdd
  *   and max, np.histogramdd)          chain.py:169-188        counts pooled over all chains, on the device)
@@ -372,6 +375,41 @@ int ipmc_histdd(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int
 int ipmc_scatter(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
                  int64_t stride_t, int64_t stride_var, const double* center, int32_t center_mode,
                  int64_t block_chains, double* scatter_out, double* dsum_out, void* stream);
+
+/* Pooled sort and rank scores (ranks.rank_normalize / pooled_quantiles / rank_convergence: the rank-normalised
+   split-R-hat with bulk and tail ESS, and exact pooled quantiles).  Additive to ABI 13.
+   The samples have ipmc_split_stats' geometry (float or double, widened to double exactly), 1 <= k <= 256.
+   The pooled index of sample t of chain c is p = c*len + t, and S = n_chains*len < 2^32 (the permutation is
+   uint32; more is IPMC_ERR_INVALID).  n_chains == 0 is a no-op.  Nothing is allocated, the host is never
+   synchronised, no workgroup waits on another, counters are integers: two calls give the same bits.
+
+   ipmc_sort_workspace: *bytes_out = the bytes of device workspace ipmc_pooled_sort needs for this geometry
+   (a second key and permutation buffer, the digit counts of every tile of IPMC_SORT_TILE keys, the plan of
+   the passes). */
+#define IPMC_SORT_TILE 4096
+int ipmc_sort_workspace(int64_t n_chains, int64_t len, int32_t k, int32_t dtype, int64_t* bytes_out);
+
+/* sorted_out[v, :] (double [k, S]) = the S values of component v ascending -- |x - fold_center[v]|, computed
+   in double, where fold_center (device, double [k]) is not NULL -- and perm_out[v, j] (uint32 [k, S]) = the
+   pooled index of the j-th smallest.  The sort is stable (equal values keep ascending p); -0.0 == +0.0 (the
+   sign of a zero in sorted_out is unspecified); NaN of any payload sorts after +inf, stable among NaNs: both
+   outputs are pure functions of the input and equal np.sort / np.argsort(kind="stable") of the column.
+   A segmented LSD radix sort with 8-bit digits over the order-preserving 64-bit image of the double; a pass
+   whose digit is the same for every key of a component is skipped.  workspace: device, 8-byte aligned,
+   workspace_bytes >= ipmc_sort_workspace's value (else IPMC_ERR_INVALID), overwritten. */
+int ipmc_pooled_sort(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t stride_chain,
+                     int64_t stride_t, int64_t stride_var, const double* fold_center, double* sorted_out,
+                     uint32_t* perm_out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* From ipmc_pooled_sort's outputs: with [a, b] the run of positions holding a value == sorted[v, j] (0-based),
+   the average rank r = (a + b)/2 + 1 (exact in double); mode 0 writes r, mode 1 the normal score
+   z = Phi^-1((r - 3/8)/(S + 1/4)) (Wichura's AS241 PPND16 from + - * / sqrt in a fixed order), at the sample's
+   own place out[c*out_stride_chain + t*out_stride_t + v*out_stride_var], (c, t) from perm[v, j].  A NaN sample
+   receives NaN.  No lane walks a run: a constant component costs what any other does.  The one launch needs no
+   workspace: workspace may be NULL and workspace_bytes any value >= 0. */
+int ipmc_rank_scores(const double* sorted, const uint32_t* perm, int32_t k, int64_t n_chains, int64_t len,
+                     int32_t mode, double* out, int64_t out_stride_chain, int64_t out_stride_t,
+                     int64_t out_stride_var, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Lorenz-96 layout of a ONE-step launch (no speculation) when lanes_per_chain = chains_per_lane = 0:
    returns lanes_per_chain, and chains_per_lane * 100 + lanes_per_chain from ipmc_auto_layout.

@@ -43,8 +43,12 @@ from .diagnostics import convergence, moments_convergence, split_rhat
 from .covariance import multivariate_rhat, posterior_covariance
 from .posterior import (hist_quantiles, histogramdd, marginal_histograms, support, wasserstein_1d,
                         wasserstein_distance, wasserstein_to_point)
+from .ranks import pooled_quantiles, rank_convergence, rank_normalize
 
 __all__ = [
+    "rank_convergence",
+    "rank_normalize",
+    "pooled_quantiles",
     "convergence",
     "split_rhat",
     "moments_convergence",

@@ -13,6 +13,7 @@ ARITH_FMA, ARITH_REFERENCE = 0, 1
 DT_FIXED, DT_CFL = 0, 1
 PROPOSAL_PCN, PROPOSAL_RW = 0, 1
 CENTER_SHARED, CENTER_SPLIT = 0, 1
+SORT_TILE = 4096  # IPMC_SORT_TILE: keys of one workgroup's tile of ipmc_pooled_sort
 
 STATUS_NAMES = {
     OK: "IPMC_OK",
@@ -168,6 +169,17 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
          C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "ipmc_sort_workspace": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "ipmc_pooled_sort": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "ipmc_rank_scores": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+         C.c_int64, C.c_void_p, C.c_int64, C.c_void_p],
     ),
     "ipmc_auto_lanes": (C.c_int, [C.POINTER(IpmcModel), C.c_int32, C.c_int64]),
     "ipmc_auto_layout": (C.c_int, [C.POINTER(IpmcModel), C.c_int32, C.c_int64]),

@@ -274,6 +274,8 @@ def _finish(mean, W, Bn, acov, C, n, N, L):
             # tau <= 0 (a first pair below zero) has no finite-variance reading: report the cap
             ess = np.where(ok, np.where(tau > 0, np.minimum(M * N / np.where(tau > 0, tau, 1.0), cap), cap), np.nan)
             out.update(ess=ess, mcse=np.sqrt(varp / ess), tau=tau, lag_used=lag_used, truncated=truncated)
+            # ranks._finish_quiet filters this warning by its text and restates this rule (ok & ~truncated)
+            # to name the components of its parts in one warning: change the three together
             short = np.flatnonzero(ok & ~truncated)
             if len(short):
                 warnings.warn(f"convergence: max_lag={L} ended the autocorrelation sum before a negative pair for "
