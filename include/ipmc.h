@@ -39,6 +39,10 @@
  *   (nothing: the reference runs one chain)                   ipmc_sort_workspace, ipmc_pooled_sort, ipmc_rank_scores
  *                                                             (rank-normalised split-R-hat, bulk / tail ESS and
  *                                                             exact pooled quantiles from one sort on the device)
+ *   (nothing: the reference runs one chain)                   ipmc_smc_workspace, ipmc_temper_sums, ipmc_temper_cumweights,
+ *                                                             ipmc_systematic_ancestors, ipmc_gather_rows
+ *                                                             (tempered SMC over the ensemble: weights, the ESS search,
+ *                                                             systematic resampling and the gather, on the device)
  *   wasserstein_distance's inputs     helpers.py:57-77,       ipmc_minmax, ipmc_hist1d, ipmc_histdd
  *   (intervals from the data's min    burgers_wasserstein_    (support, marginal and joint np.histogramdd
  *   and max, np.histogramdd)          chain.py:169-188        counts pooled over all chains, on the device)
@@ -410,6 +414,56 @@ int ipmc_pooled_sort(const void* x, int32_t dtype, int64_t n_chains, int64_t len
 int ipmc_rank_scores(const double* sorted, const uint32_t* perm, int32_t k, int64_t n_chains, int64_t len,
                      int32_t mode, double* out, int64_t out_stride_chain, int64_t out_stride_t,
                      int64_t out_stride_var, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Tempered sequential Monte Carlo over the ensemble (smc.TemperedSMC: reweight, the ESS search for the next
+   temperature, systematic resampling, the gather of the particle states).  Additive to ABI 13.
+   Device pointers, asynchronous on `stream`, nothing allocated, the host never synchronised, no floating-point
+   atomics, every sum in a fixed order that depends on the arguments alone: two calls give the same bits, and
+   the twins of ipmc_host.h give them on the host.  n == 0 is a no-op.  All arithmetic is double without FMA.
+
+   The weight of particle c for the temperature increment delta >= 0 (finite) is
+     w_c(delta) = det_exp(-(delta * ((double)phi[c] - phi_ref)))        (csrc/ipmc_exp.hpp),
+   and exactly 0 where phi[c] is not finite (an invalid forward map).  phi: float or double [n], widened
+   exactly; phi_ref: the smallest finite phi, so that the largest weight is exactly 1 (a phi below phi_ref is
+   outside det_exp's range and gives NaN).  A block is IPMC_SMC_BLOCK consecutive particles, the posterior
+   mean's block (ipmc_block_sums as shard.block_sum calls it).
+
+   ipmc_smc_workspace: *bytes_out = the device workspace ipmc_temper_sums (n_deltas candidates) and
+   ipmc_temper_cumweights need for n particles (the blocks' sums). */
+#define IPMC_SMC_BLOCK 1024
+#define IPMC_SMC_MAX_DELTAS 64
+int ipmc_smc_workspace(int64_t n, int32_t n_deltas, int64_t* bytes_out);
+
+/* s1_out[j] = Σ_c w_c(deltas[j]), s2_out[j] = Σ_c w_c(deltas[j])², device double [n_deltas] each, for
+   1 <= n_deltas <= IPMC_SMC_MAX_DELTAS candidates in one pass over phi.  Each sum: inside every block from zero
+   in particle order, then the blocks' sums from zero in block order.  deltas is a HOST array read during the
+   call (the exception ipmc_histdd makes for comp / bins).  workspace: device, 8-byte aligned, overwritten. */
+int ipmc_temper_sums(const void* phi, int32_t dtype, int64_t n, double phi_ref, const double* deltas,
+                     int32_t n_deltas, double* s1_out, double* s2_out, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
+/* cum_out[c] (double [n]) = offset[b] + within[c]: within = the running sum of w(delta) inside the block b of c
+   from zero in particle order, offset[b] = the running sum of the earlier blocks' totals from zero in block
+   order.  Non-decreasing; the total is cum_out[n - 1]; cum_out[c] > cum_out[c - 1] only where w_c > 0. */
+int ipmc_temper_cumweights(const void* phi, int32_t dtype, int64_t n, double phi_ref, double delta,
+                           double* cum_out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Systematic resampling from non-decreasing cumulative weights cum (double [n]): with total = cum[n - 1] (read on
+   the device), step = total / (double)n_out and p_i = ((double)i + u) * step, anc_out[i] (int64 [n_out]) = the
+   smallest c with cum[c] > p_i; where there is none (p_i >= total by rounding) the first c with
+   cum[c] == total, which is the last at which cum rises.  Either way cum[c] > cum[c - 1] (cum[0] > 0 for c = 0):
+   a particle of weight 0 is never an ancestor, and anc_out is non-decreasing.  total not a positive finite
+   number: every entry is -1.  0 <= u < 1 is a host double.  One binary search per offspring. */
+int ipmc_systematic_ancestors(const double* cum, int64_t n, double u, int64_t n_out, int64_t* anc_out,
+                              void* stream);
+
+/* dst[i*dst_stride + j] = src[idx[i]*src_stride + j] for i < n_out, j < k, out of place (dst must not overlap
+   src); float or double, strides in elements and >= k, 1 <= k <= 256, idx int64 [n_out].  An index outside
+   [0, n_src) leaves its destination row untouched and reads nothing.  Consecutive lanes copy consecutive
+   elements of the rows of a tile, so short rows share a wave; after resampling idx is non-decreasing with
+   runs of repeats and the reads are nearly sequential. */
+int ipmc_gather_rows(const void* src, int32_t dtype, int64_t n_src, int32_t k, int64_t src_stride,
+                     const int64_t* idx, int64_t n_out, void* dst, int64_t dst_stride, void* stream);
 
 /* Lorenz-96 layout of a ONE-step launch (no speculation) when lanes_per_chain = chains_per_lane = 0:
    returns lanes_per_chain, and chains_per_lane * 100 + lanes_per_chain from ipmc_auto_layout.

@@ -21,6 +21,11 @@
  *   ipmc_host_ordered_sum    the chain-ordered sum behind the posterior mean over
  *                        many chains (shard.ordered_mean; np.mean over samples
  *                        in the reference's one-chain scripts)
+ *   ipmc_host_temper_sums, ipmc_host_temper_cumweights, ipmc_host_systematic_ancestors
+ *                        (nothing: the reference runs one chain) the weights, cumulative
+ *                        weights and ancestors of tempered SMC over the ensemble
+ *                        (smc.py), from csrc/ipmc_exp.hpp; twins of ipmc_temper_sums,
+ *                        ipmc_temper_cumweights and ipmc_systematic_ancestors
  *
  * Host pointers only.  Returns IPMC_OK (0) or an IPMC_ERR_* code of ipmc.h;
  * ipmc_host_last_error() gives the message (thread-local).
@@ -68,6 +73,17 @@ int ipmc_host_step_uniforms(uint64_t seed, int64_t chain, uint64_t step, int32_t
  * (the reduction a many-chain run adds). */
 int ipmc_host_ordered_sum(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride, double div,
                           double* acc);
+
+/* Tempered SMC (smc.py): the host twins of ipmc_temper_sums, ipmc_temper_cumweights and
+ * ipmc_systematic_ancestors (ipmc.h, where the definitions are): the same operations in the same order
+ * from the same ipmc_exp.hpp, bit-identical to the kernels, on host pointers, with no workspace.  They are
+ * what the kernels are tested against and the resampling of a run on a machine without a GPU.  (The twin of
+ * ipmc_gather_rows is numpy's x[idx].)  The reference has no counterpart: it runs one chain. */
+int ipmc_host_temper_sums(const void* phi, int32_t dtype, int64_t n, double phi_ref, const double* deltas,
+                          int32_t n_deltas, double* s1_out, double* s2_out);
+int ipmc_host_temper_cumweights(const void* phi, int32_t dtype, int64_t n, double phi_ref, double delta,
+                                double* cum_out);
+int ipmc_host_systematic_ancestors(const double* cum, int64_t n, double u, int64_t n_out, int64_t* anc_out);
 
 #ifdef __cplusplus
 }

@@ -44,8 +44,14 @@ from .covariance import multivariate_rhat, posterior_covariance
 from .posterior import (hist_quantiles, histogramdd, marginal_histograms, support, wasserstein_1d,
                         wasserstein_distance, wasserstein_to_point)
 from .ranks import pooled_quantiles, rank_convergence, rank_normalize
+from .smc import SMCResult, TemperedSMC, next_temperature, systematic_resample, tempering_sums
 
 __all__ = [
+    "TemperedSMC",
+    "SMCResult",
+    "tempering_sums",
+    "next_temperature",
+    "systematic_resample",
     "rank_convergence",
     "rank_normalize",
     "pooled_quantiles",

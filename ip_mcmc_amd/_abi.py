@@ -14,6 +14,8 @@ DT_FIXED, DT_CFL = 0, 1
 PROPOSAL_PCN, PROPOSAL_RW = 0, 1
 CENTER_SHARED, CENTER_SPLIT = 0, 1
 SORT_TILE = 4096  # IPMC_SORT_TILE: keys of one workgroup's tile of ipmc_pooled_sort
+SMC_BLOCK = 1024  # IPMC_SMC_BLOCK: particles of one block of the tempering sums
+SMC_MAX_DELTAS = 64  # IPMC_SMC_MAX_DELTAS: candidates of one ipmc_temper_sums call
 
 STATUS_NAMES = {
     OK: "IPMC_OK",
@@ -180,6 +182,22 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
          C.c_int64, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "ipmc_smc_workspace": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "ipmc_temper_sums": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_int64, C.c_void_p],
+    ),
+    "ipmc_temper_cumweights": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "ipmc_systematic_ancestors": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ipmc_gather_rows": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+         C.c_void_p],
     ),
     "ipmc_auto_lanes": (C.c_int, [C.POINTER(IpmcModel), C.c_int32, C.c_int64]),
     "ipmc_auto_layout": (C.c_int, [C.POINTER(IpmcModel), C.c_int32, C.c_int64]),

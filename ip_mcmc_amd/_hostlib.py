@@ -27,6 +27,9 @@ SIGNATURES = {
     "ipmc_host_uniform": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_uint64, _P]),
     "ipmc_host_step_uniforms": (C.c_int, [C.c_uint64, C.c_int64, C.c_uint64, C.c_int32, _P]),
     "ipmc_host_ordered_sum": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_double, _P]),
+    "ipmc_host_temper_sums": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_double, _P, C.c_int32, _P, _P]),
+    "ipmc_host_temper_cumweights": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_double, C.c_double, _P]),
+    "ipmc_host_systematic_ancestors": (C.c_int, [_P, C.c_int64, C.c_double, C.c_int64, _P]),
 }
 
 _lib = None
@@ -107,3 +110,39 @@ def ordered_sum(rows, acc, div=1.0):
     assert acc.dtype == np.float64 and acc.flags.c_contiguous and acc.shape[0] == a.shape[1]
     call("ipmc_host_ordered_sum", _ptr(a), a.shape[0], a.shape[1], a.shape[1], float(div), _ptr(acc))
     return acc
+
+
+def _phi_array(phi):
+    a = np.asarray(phi)
+    if a.dtype != np.float32:
+        a = a.astype(np.float64, copy=False)
+    a = np.ascontiguousarray(a)
+    if a.ndim != 1:
+        raise ValueError("phi must be one-dimensional")
+    return a, (_abi.F32 if a.dtype == np.float32 else _abi.F64)
+
+
+def temper_sums(phi, phi_ref, deltas):
+    """(s1, s2) float64 (len(deltas),): Σ w and Σ w² of the tempering weights, the host twin of
+    ipmc_temper_sums (at most 64 candidates)."""
+    a, dt = _phi_array(phi)
+    d = np.ascontiguousarray(np.atleast_1d(deltas), dtype=np.float64)
+    s1, s2 = np.zeros(d.shape[0]), np.zeros(d.shape[0])
+    call("ipmc_host_temper_sums", _ptr(a), dt, a.shape[0], float(phi_ref), _ptr(d), d.shape[0], _ptr(s1), _ptr(s2))
+    return s1, s2
+
+
+def temper_cumweights(phi, phi_ref, delta):
+    """cum float64 (n,): the cumulative tempering weights, the host twin of ipmc_temper_cumweights."""
+    a, dt = _phi_array(phi)
+    cum = np.empty(a.shape[0], dtype=np.float64)
+    call("ipmc_host_temper_cumweights", _ptr(a), dt, a.shape[0], float(phi_ref), float(delta), _ptr(cum))
+    return cum
+
+
+def systematic_ancestors(cum, u, n_out):
+    """ancestors int64 (n_out,): the host twin of ipmc_systematic_ancestors."""
+    c = np.ascontiguousarray(cum, dtype=np.float64)
+    anc = np.full(int(n_out), -1, dtype=np.int64)
+    call("ipmc_host_systematic_ancestors", _ptr(c), c.shape[0], float(u), int(n_out), _ptr(anc))
+    return anc

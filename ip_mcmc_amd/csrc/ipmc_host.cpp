@@ -9,6 +9,7 @@
 
 #include "../../include/ipmc.h"
 #include "../../include/ipmc_host.h"
+#include "ipmc_exp.hpp"
 #include "ipmc_rng.hpp"
 
 using namespace ipmc;
@@ -73,6 +74,48 @@ void draws(uint64_t seed, int64_t c_off, int64_t n, uint64_t step0, int64_t tota
       if (j == 0 && log_r) log_r[sc] = det_log(accept_uniform(seed, gid, step));
     }
   });
+}
+
+constexpr int64_t kSmcBlock = IPMC_SMC_BLOCK;
+
+// w_c(delta) of particle c (ipmc_exp.hpp: smc_weight), Φ widened exactly
+template <typename T>
+inline double weight_of(const T* phi, int64_t c, double phi_ref, double delta) {
+  return smc_weight((double)phi[c], phi_ref, delta);
+}
+
+template <typename T>
+void temper_sums(const T* phi, int64_t n, double phi_ref, const double* deltas, int nd, double* s1, double* s2) {
+  for (int j = 0; j < nd; ++j) {
+    double t1 = 0.0, t2 = 0.0;  // the block sums from zero in block order
+    for (int64_t b0 = 0; b0 < n; b0 += kSmcBlock) {
+      const int64_t b1 = std::min(n, b0 + kSmcBlock);
+      double a1 = 0.0, a2 = 0.0;  // one block from zero in particle order
+      for (int64_t c = b0; c < b1; ++c) {
+        const double w = weight_of(phi, c, phi_ref, deltas[j]);
+        a1 = a1 + w;
+        a2 = a2 + w * w;
+      }
+      t1 = t1 + a1;
+      t2 = t2 + a2;
+    }
+    s1[j] = t1;
+    s2[j] = t2;
+  }
+}
+
+template <typename T>
+void temper_cumweights(const T* phi, int64_t n, double phi_ref, double delta, double* cum) {
+  double offset = 0.0;
+  for (int64_t b0 = 0; b0 < n; b0 += kSmcBlock) {
+    const int64_t b1 = std::min(n, b0 + kSmcBlock);
+    double within = 0.0;
+    for (int64_t c = b0; c < b1; ++c) {
+      within = within + weight_of(phi, c, phi_ref, delta);
+      cum[c] = offset + within;
+    }
+    offset = offset + within;
+  }
 }
 
 }  // namespace
@@ -166,6 +209,71 @@ int ipmc_host_ordered_sum(const double* rows, int64_t n_rows, int64_t k, int64_t
       for (int64_t j = 0; j < k; ++j) ap[j] = ap[j] + x[j] / div;
   }
   for (int64_t j = 0; j < k; ++j) acc[j] = ap[j];
+  return IPMC_OK;
+}
+
+int ipmc_host_temper_sums(const void* phi, int32_t dtype, int64_t n, double phi_ref, const double* deltas,
+                          int32_t n_deltas, double* s1_out, double* s2_out) {
+  if (n < 0 || n_deltas < 0) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: negative size");
+  if (n == 0) return IPMC_OK;
+  if (n_deltas < 1 || n_deltas > IPMC_SMC_MAX_DELTAS)
+    return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: n_deltas = %d outside [1, %d]", n_deltas,
+                IPMC_SMC_MAX_DELTAS);
+  if (dtype != IPMC_F32 && dtype != IPMC_F64) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: bad dtype");
+  if (!phi || !deltas || !s1_out || !s2_out) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: NULL pointer");
+  for (int j = 0; j < n_deltas; ++j)
+    if (!(deltas[j] >= 0.0) || !(deltas[j] < __builtin_inf()))
+      return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: deltas[%d] is not a finite number >= 0", j);
+  if (dtype == IPMC_F64)
+    temper_sums((const double*)phi, n, phi_ref, deltas, n_deltas, s1_out, s2_out);
+  else
+    temper_sums((const float*)phi, n, phi_ref, deltas, n_deltas, s1_out, s2_out);
+  return IPMC_OK;
+}
+
+int ipmc_host_temper_cumweights(const void* phi, int32_t dtype, int64_t n, double phi_ref, double delta,
+                                double* cum_out) {
+  if (n < 0) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_cumweights: negative size");
+  if (n == 0) return IPMC_OK;
+  if (dtype != IPMC_F32 && dtype != IPMC_F64)
+    return fail(IPMC_ERR_INVALID, "ipmc_host_temper_cumweights: bad dtype");
+  if (!phi || !cum_out) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_cumweights: NULL pointer");
+  if (!(delta >= 0.0) || !(delta < __builtin_inf()))
+    return fail(IPMC_ERR_INVALID, "ipmc_host_temper_cumweights: delta is not a finite number >= 0");
+  if (dtype == IPMC_F64)
+    temper_cumweights((const double*)phi, n, phi_ref, delta, cum_out);
+  else
+    temper_cumweights((const float*)phi, n, phi_ref, delta, cum_out);
+  return IPMC_OK;
+}
+
+int ipmc_host_systematic_ancestors(const double* cum, int64_t n, double u, int64_t n_out, int64_t* anc_out) {
+  if (n < 0 || n_out < 0) return fail(IPMC_ERR_INVALID, "ipmc_host_systematic_ancestors: negative size");
+  if (!(u >= 0.0 && u < 1.0)) return fail(IPMC_ERR_INVALID, "ipmc_host_systematic_ancestors: u outside [0, 1)");
+  if (n == 0 || n_out == 0) return IPMC_OK;
+  if (!anc_out || !cum) return fail(IPMC_ERR_INVALID, "ipmc_host_systematic_ancestors: NULL pointer");
+  const double total = cum[n - 1];
+  if (!(total > 0.0) || !(total < __builtin_inf())) {
+    for (int64_t i = 0; i < n_out; ++i) anc_out[i] = -1;
+    return IPMC_OK;
+  }
+  const double step = total / (double)n_out;
+  for (int64_t i = 0; i < n_out; ++i) {
+    const double p = ((double)i + u) * step;
+    int64_t lo = 0, hi = n;  // the smallest c with cum[c] > p; n if there is none
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (cum[mid] > p) hi = mid; else lo = mid + 1;
+    }
+    if (lo == n) {  // p >= total by rounding: the last c at which cum rises = the first that holds the total
+      lo = 0, hi = n - 1;
+      while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (cum[mid] >= total) hi = mid; else lo = mid + 1;
+      }
+    }
+    anc_out[i] = lo;
+  }
   return IPMC_OK;
 }
 
