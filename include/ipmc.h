@@ -124,7 +124,9 @@ typedef struct ipmc_model {
   const void* x0;     /* [dim] initial state (L63/L96); Burgers: [dim+2] cell centres incl. ghosts */
   const void* theta0; /* [k] prior-mean offset: the model evaluates at theta = theta0 + u */
   const void* A;      /* LINEAR: [q, k] matrix */
-  /* Burgers (IPMC_MODEL_BURGERS) */
+  /* Burgers (IPMC_MODEL_BURGERS): dim = N is a multiple of 8 and at most 512, or a multiple of 4 and at most 256
+     (8 or 4 cells on each of at most 64 lanes; lanes_per_chain > 0 asks for dim / lanes_per_chain = 4 or 8 cells);
+     any other N is IPMC_ERR_UNSUPPORTED.  At most 64 windows of at most 129 cells. */
   int32_t dt_mode;    /* ipmc_dt_mode */
   int32_t n_windows;  /* == q */
   const int32_t* win_lo; /* [q] first cell (interior index) of each trapz window  utilities.py:93-98 */

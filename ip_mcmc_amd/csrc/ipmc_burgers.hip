@@ -738,8 +738,14 @@ static int validate(const ipmc_model& m, int64_t n_chains, int lanes, int& cpl, 
     return IPMC_ERR_UNSUPPORTED;
   }
   if (!pick(m.dim, n_chains, lanes, cpl, gs) || (cpl != 4 && cpl != 8)) {
-    set_error("Burgers: N=%d must be a multiple of 4 and at most 512 (lanes_per_chain=%d: N/lanes must be 4 or 8)",
-              m.dim, lanes);
+    // 8 cells per lane on up to 64 lanes, or 4 when N is no multiple of 8
+    if (lanes > 0)
+      set_error("Burgers: N=%d lanes_per_chain=%d is not supported: N must be 4 or 8 cells on each of at most 64 lanes",
+                m.dim, lanes);
+    else
+      set_error("Burgers: N=%d is not supported: N must be a multiple of 8 and at most 512, or a multiple of 4 and at "
+                "most 256",
+                m.dim);
     return IPMC_ERR_UNSUPPORTED;
   }
   return IPMC_OK;
