@@ -682,51 +682,52 @@ static bool pick(int N, int64_t n_chains, int lanes, int& cpl, int& gs) {
 
 // Speculation width: spec_width if given (a power of two, S·GS <= 64), else for
 // multi-step launches the widest keeping the ensemble within one wave per SIMD.
-template <int GS>
-static int burgers_spec(const ipmc_sweep& s) {
+// IPMC_ERR_UNSUPPORTED with the error set for a width the kernel has no layout for.
+static int burgers_spec(const ipmc_sweep& s, int gs, int& spec) {
   if (s.spec_width > 0) {
     const int w = s.spec_width;
-    return ((w & (w - 1)) == 0 && (w * GS <= 64 || w * GS == kBurBlock)) ? w : -1;
+    if ((w & (w - 1)) != 0 || (w * gs > 64 && w * gs != kBurBlock)) {
+      set_error("Burgers: spec_width must be a power of two with spec_width * %d lanes <= 64 or = 256", gs);
+      return IPMC_ERR_UNSUPPORTED;
+    }
+    spec = w;
+    return IPMC_OK;
   }
   int w = 1;
   if (s.n_steps > 1) {
-    while (w * 2 * GS <= 64 && s.n_chains * (int64_t)GS * w * 2 <= 65536) w *= 2;
+    while (w * 2 * gs <= 64 && s.n_chains * (int64_t)gs * w * 2 <= 65536) w *= 2;
     // a whole block of slots per chain while the ensemble stays within one wave per SIMD
-    if (w * GS == 64 && s.n_chains * (int64_t)kBurBlock <= 65536) w = kBurBlock / GS;
+    if (w * gs == 64 && s.n_chains * (int64_t)kBurBlock <= 65536) w = kBurBlock / gs;
   }
-  return w;
+  spec = w;
+  return IPMC_OK;
 }
 
 template <typename T, int CPL, int GS, bool FM>
 static int launch_sweep(const ipmc_model& m, const ipmc_sweep& s, hipStream_t st) {
-  const int S = burgers_spec<GS>(s);
-  if (S < 1) {
-    set_error("Burgers: spec_width must be a power of two with spec_width * %d lanes <= 64 or = 256", GS);
-    return IPMC_ERR_UNSUPPORTED;
-  }
+  int S;
+  const int rc = burgers_spec(s, GS, S);
+  if (rc) return rc;
   const int64_t blocks = (s.n_chains * GS * S + kBurBlock - 1) / kBurBlock;
   hipLaunchKernelGGL((burgers_sweep_kernel<T, CPL, GS, FM>), dim3((unsigned)blocks), dim3(kBurBlock), 0, st, m, s,
                      S);
   return check_launch("burgers_sweep_kernel");
 }
 
-template <typename T, int CPL, int GS, bool FM>
+template <typename T, int CPL, int GS, bool FM, bool PHI>
 static int launch_eval(const ipmc_model& m, int64_t n, const void* u, const void* y, const void* ginv, void* out,
-                       bool phi, hipStream_t st) {
+                       hipStream_t st) {
   const int64_t blocks = (n * GS + kBurBlock - 1) / kBurBlock;
-  if (phi)
-    hipLaunchKernelGGL((burgers_eval_kernel<T, CPL, GS, FM, true>), dim3((unsigned)blocks), dim3(kBurBlock), 0, st,
-                       m, n, (const T*)u, (const T*)y, (const T*)ginv, (T*)out);
-  else
-    hipLaunchKernelGGL((burgers_eval_kernel<T, CPL, GS, FM, false>), dim3((unsigned)blocks), dim3(kBurBlock), 0, st,
-                       m, n, (const T*)u, (const T*)y, (const T*)ginv, (T*)out);
+  hipLaunchKernelGGL((burgers_eval_kernel<T, CPL, GS, FM, PHI>), dim3((unsigned)blocks), dim3(kBurBlock), 0, st, m,
+                     n, (const T*)u, (const T*)y, (const T*)ginv, (T*)out);
   return check_launch("burgers_eval_kernel");
 }
 
-template <typename T, bool FM, typename F>
-static int dispatch(int cpl, int gs, F&& f) {
+// The compiled (CPL, GS) layouts: f(cpl, gs) with integral_constant tags.
+template <typename F>
+static int with_layout(int cpl, int gs, F&& f) {
 #define IPMC_BUR(C, G) \
-  if (cpl == C && gs == G) return f.template operator()<T, C, G, FM>();
+  if (cpl == C && gs == G) return f(std::integral_constant<int, C>{}, std::integral_constant<int, G>{});
   IPMC_BUR(8, 16) IPMC_BUR(8, 32) IPMC_BUR(8, 64) IPMC_BUR(4, 16) IPMC_BUR(4, 32) IPMC_BUR(4, 64)
 #undef IPMC_BUR
   return IPMC_ERR_UNSUPPORTED;
@@ -751,37 +752,18 @@ static int validate(const ipmc_model& m, int64_t n_chains, int lanes, int& cpl, 
   return IPMC_OK;
 }
 
-struct SweepLauncher {
-  const ipmc_model& m;
-  const ipmc_sweep& s;
-  hipStream_t st;
-  template <typename T, int C, int G, bool FM>
-  int operator()() {
-    return launch_sweep<T, C, G, FM>(m, s, st);
-  }
-};
-
-struct EvalLauncher {
-  const ipmc_model& m;
-  int64_t n;
-  const void *u, *y, *ginv;
-  void* out;
-  bool phi;
-  hipStream_t st;
-  template <typename T, int C, int G, bool FM>
-  int operator()() {
-    return launch_eval<T, C, G, FM>(m, n, u, y, ginv, out, phi, st);
-  }
-};
-
 int burgers_sweep(const ipmc_model& m, const ipmc_sweep& s, hipStream_t st) {
   int cpl, gs;
-  int rc = validate(m, s.n_chains, s.lanes_per_chain, cpl, gs);
+  const int rc = validate(m, s.n_chains, s.lanes_per_chain, cpl, gs);
   if (rc) return rc;
-  SweepLauncher l{m, s, st};
-  const bool fm = m.arith == IPMC_ARITH_FMA;
-  if (s.dtype == IPMC_F64) return fm ? dispatch<double, true>(cpl, gs, l) : dispatch<double, false>(cpl, gs, l);
-  return fm ? dispatch<float, true>(cpl, gs, l) : dispatch<float, false>(cpl, gs, l);
+  return with_dtype(s.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return with_bool(m.arith == IPMC_ARITH_FMA, [&](auto fm) {
+      return with_layout(cpl, gs, [&](auto c, auto g) {
+        return launch_sweep<T, decltype(c)::value, decltype(g)::value, decltype(fm)::value>(m, s, st);
+      });
+    });
+  });
 }
 
 int burgers_plan(const ipmc_model& m, const ipmc_sweep& s, int& lanes, int& spec) {
@@ -789,23 +771,25 @@ int burgers_plan(const ipmc_model& m, const ipmc_sweep& s, int& lanes, int& spec
   const int rc = validate(m, s.n_chains, s.lanes_per_chain, cpl, gs);
   if (rc) return rc;
   lanes = gs;
-  spec = gs == 16 ? burgers_spec<16>(s) : gs == 32 ? burgers_spec<32>(s) : burgers_spec<64>(s);
-  if (spec < 1) {
-    set_error("Burgers: spec_width must be a power of two with spec_width * %d lanes <= 64 or = 256", gs);
-    return IPMC_ERR_UNSUPPORTED;
-  }
-  return IPMC_OK;
+  return burgers_spec(s, gs, spec);
 }
 
 int burgers_eval(const ipmc_model& m, int32_t dtype, int64_t n, const void* u, const void* y, const void* ginv,
                  void* out, bool phi, hipStream_t st) {
   int cpl, gs;
-  int rc = validate(m, n, 0, cpl, gs);
+  const int rc = validate(m, n, 0, cpl, gs);
   if (rc) return rc;
-  EvalLauncher l{m, n, u, y, ginv, out, phi, st};
-  const bool fm = m.arith == IPMC_ARITH_FMA;
-  if (dtype == IPMC_F64) return fm ? dispatch<double, true>(cpl, gs, l) : dispatch<double, false>(cpl, gs, l);
-  return fm ? dispatch<float, true>(cpl, gs, l) : dispatch<float, false>(cpl, gs, l);
+  return with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return with_bool(m.arith == IPMC_ARITH_FMA, [&](auto fm) {
+      return with_bool(phi, [&](auto ph) {
+        return with_layout(cpl, gs, [&](auto c, auto g) {
+          return launch_eval<T, decltype(c)::value, decltype(g)::value, decltype(fm)::value, decltype(ph)::value>(
+              m, n, u, y, ginv, out, st);
+        });
+      });
+    });
+  });
 }
 
 }  // namespace ipmc

@@ -15,7 +15,7 @@
 // Lane k accumulates the five moments of slot k; Φ sums the 5K residuals in
 // observation order (every lane gathers them, so all lanes hold Φ).
 #include "ipmc_internal.hpp"
-#include "ipmc_sweep_common.hpp"
+#include "ipmc_spec_round.hpp"
 
 namespace ipmc {
 
@@ -526,145 +526,16 @@ __global__ __launch_bounds__(kTsBlock, (ts_waves<T, J, SPL>())) void l96ts_sweep
   const int K = m.dim, L = K / SPL, G = S * L;
   const int cpw = 64 / G;
   const int q = lane / G, r = lane - q * G;
-  const int slot = r / L;
   const int cbase = q * G;  // the chain's first lane in the wave
-  TsCtx c{K, r - slot * L, cbase + slot * L};
+  const TsCtx c{K, r % L, lane - r % L};
   const int64_t chain = q < cpw ? (((int64_t)blockIdx.x * kTsBlock + threadIdx.x) >> 6) * cpw + q : -1;
   if (chain < 0 || chain >= s.n_chains) return;
-  const uint64_t gid = (uint64_t)(s.chain_offset + chain);
-  T* u = (T*)s.u + chain * 3;
-  T ur[3] = {u[0], u[1], u[2]};
-  const T* sq = (const T*)s.prior_sqrt;
-  const T beta = (T)s.beta, contr = (T)s.contraction;
-  const bool rw = (s.proposal == IPMC_PROPOSAL_RW);
-  T* phi = (T*)s.phi;
-  T phu = phi[chain];
-  int nacc = 0, ncalls = 0;
-  SampleClock clk(s);
-  int64_t st = 0;
-  SpecGuess guess(spec_accept_prior(s, chain));  // the speculation tree (ipmc_sweep_common.hpp)
-  const T* chol = (const T*)s.prior_chol;
-  const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1);
-  while (st < s.n_steps) {
-    const int64_t left = s.n_steps - st;
-    const int tb = S > 1 ? guess.bucket() : 0;
-    const SpecNode nd = kSpecTrees.nd[tb][slot];
-    const int maxlvl = kSpecTrees.maxlvl[tb][S];
-    const bool act = nd.depth < left;  // uniform per slot
-    const int64_t tt = st + nd.depth;
-    const int ol = cbase + (nd.orig < 0 ? 0 : nd.orig) * L;  // the origin slot's first lane
+  spec_sweep3<T, FM, kTsBlock>(s, S, chain, r, L, cbase, vpk, [&](const T(&v)[3]) {
+    // k behind an opaque register copy made once per pCN step (ts_phi)
     int kq = c.sub;
     asm volatile("" : "+v"(kq));
-    bool ok = false, acc = false;
-    T phv = (T)0;
-    double lr = 0.0;
-    const uint64_t step = s.step0 + (uint64_t)tt;
-    T w[3];
-    if (act) pcn_noise<T, 3>(sq, s.seed, gid, step, 0, w, chol, 3);
-    const T bs = (act && s.beta_schedule) ? (T)s.beta_schedule[2 * tt] : beta;
-    const T cs = (act && s.beta_schedule) ? (T)s.beta_schedule[2 * tt + 1] : contr;
-    // the proposals level by level (every lane of a slot holds its proposal):
-    // a node's origin was formed one level before
-    T v[3] = {(T)0, (T)0, (T)0};
-    for (int lv = 0; lv <= maxlvl; ++lv) {
-      T o[3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) o[j] = __shfl(v[j], ol, 64);
-      if (act && nd.lvl == lv) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) v[j] = propose_one<T>(rw, nd.orig < 0 ? ur[j] : o[j], w[j], cs, bs);
-      }
-    }
-    if (act) {  // uniform per slot
-      ok = true;
-      if (s.box_lo || s.box_hi) {
-        const T* lo = (const T*)s.box_lo;
-        const T* hi = (const T*)s.box_hi;
-        const T* off = (const T*)s.box_off;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const T t = v[j] + (off ? off[j] : (T)0);
-          if (lo && !(lo[j] < t)) ok = false;
-          if (hi && !(t < hi[j])) ok = false;
-        }
-      }
-      if (ok) {
-        phv = ts_phi<T, J, FM, SPL>(m, v, c, kq, (const T*)s.y, (const T*)s.gamma_inv, nullptr);
-        if (s.reg_scale) phv = phv + regularizer<T, 3, 1, FM>((const T*)s.reg_scale, v, lane);
-        lr = det_log(accept_uniform(s.seed, gid, step));
-      }
-    }
-    // pcn_accept against the state this node proposed from: the chain's, or
-    // its origin node's proposal (whose Φ that slot's lanes hold)
-    const T pho = __shfl(phv, ol, 64);
-    if (ok) acc = (double)((nd.orig < 0 ? phu : pho) - phv) > lr;
-    // one bit per slot (its first lane, at bit slot*L of the chain's lanes); the
-    // walk resolved in parallel (spec_on_path, as ipmc_l96.hpp): no cross-lane
-    // read inside a data-dependent loop
-    const unsigned long long accm = spec_slot_bits((__ballot(acc && c.sub == 0) >> cbase) & gmask, S, L);
-    const unsigned long long okm = spec_slot_bits((__ballot(ok && c.sub == 0) >> cbase) & gmask, S, L);
-    const unsigned long long path =
-        spec_slot_bits((__ballot(spec_on_path(tb, slot, accm, act) && c.sub == 0) >> cbase) & gmask, S, L);
-    const SpecRound rd = spec_path_round(path, accm, okm);
-    const int wl = cbase + (rd.win >= 0 ? rd.win : 0) * L;  // the new state's slot, first lane
-    T vf[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) vf[j] = __shfl(v[j], wl, 64);
-    const T phf = __shfl(phv, wl, 64);
-    if (s.sum_u || s.sample_every > 0) {  // uniform per chain (only lane r == 0 keeps the clock)
-      // the states after each settled step, in step order: the path again, the
-      // proposals read from the LDS park, written by lane r == 0
-      const bool sums = s.sum_u && r == 0;
-      RoundSums<3> rsum(sums ? s.sum_u + chain * 3 : nullptr, (sums && s.sum_u2) ? s.sum_u2 + chain * 3 : nullptr,
-                        sums ? 3 : 0);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) vpk[j][threadIdx.x] = v[j];
-      wave_sync_lds();
-      const int t0 = (threadIdx.x & ~63) + cbase;  // the chain's first thread in the block
-      spec_path_replay(
-          path, accm,
-          [&](int q, int la) {
-            T vq[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) vq[j] = vpk[j][t0 + (la >= 0 ? la : 0) * L];
-            if (r == 0) {
-              if (sums) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) rsum.add(j, la >= 0 ? (double)vq[j] : (double)ur[j]);
-              }
-              if (s.sample_every > 0 && clk.next == st + q) {
-                const int64_t sl = clk.take(clk.next);
-                T* so = (T*)s.sample_out + chain * s.sample_stride + sl * s.sample_step_stride;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) so[j] = la >= 0 ? vq[j] : ur[j];
-              }
-            }
-          });
-      if (sums) rsum.store();
-      wave_sync_lds();  // the park is rewritten next round
-    }
-    if (rd.win >= 0) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) ur[j] = vf[j];
-      phu = phf;
-    }
-    nacc += rd.nar;
-    ncalls += rd.calls;
-    guess.settle(rd.nar, rd.used);
-    st += rd.used;
-  }
-  if (r == 0) {
-    phi[chain] = phu;
-    if (s.accepts) s.accepts[chain] += nacc;
-    if (s.calls) s.calls[chain] += ncalls;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) u[j] = ur[j];
-    if (s.sample_out && s.sample_every == 0) {
-      T* so = (T*)s.sample_out + chain * s.sample_stride;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) so[j] = ur[j];
-    }
-  }
+    return ts_phi<T, J, FM, SPL>(m, v, c, kq, (const T*)s.y, (const T*)s.gamma_inv, nullptr);
+  });
 }
 
 template <typename T, int J, bool FM, int SPL, bool PHI>
@@ -722,131 +593,110 @@ static int ts_spl(const ipmc_model& m, const ipmc_sweep* s) {
 
 // Speculation width: spec_width if given (S·L <= 64), else, for multi-step
 // launches, the widest that keeps the ensemble within one wave per SIMD.
-static int ts_spec(const ipmc_sweep& s, int L) {
+static int ts_spec(const ipmc_sweep& s, int L, int& spec) {
   const int smax = 64 / L;
-  if (s.spec_width > 0) return s.spec_width <= smax ? s.spec_width : -1;
-  if (s.n_steps <= 1) return 1;
-  const int64_t fit = 65536 / (s.n_chains * (int64_t)L);
-  return (int)(fit < 1 ? 1 : (fit > smax ? smax : fit));
-}
-
-template <typename T, bool FM, int SPL>
-static int ts_sweep_t(const ipmc_model& m, const ipmc_sweep& s, hipStream_t st) {
-  const int L = m.dim / SPL;
-  const int S = ts_spec(s, L);
-  if (S < 1) {
+  if (s.spec_width > smax) {
     set_error("two-scale Lorenz-96: spec_width * lanes per chain (%d) must be <= 64", L);
     return IPMC_ERR_UNSUPPORTED;
   }
-  const int64_t blocks = ts_blocks(L * S, s.n_chains);
-  switch (m.fast_per_slow) {
-#define IPMC_J(J)                                                                                                  \
-  case J:                                                                                                          \
-    if constexpr (ts_compiled<SPL, J>()) {                                     \
-      hipLaunchKernelGGL((l96ts_sweep_kernel<T, J, FM, SPL>), dim3((unsigned)blocks), dim3(kTsBlock), 0, st, m, s, \
-                         S);                                                                                       \
-      return check_launch("l96ts_sweep_kernel");                                                                   \
-    }                                                                                                              \
-    break;
-    IPMC_TS_J(IPMC_J)
-#undef IPMC_J
+  spec = 1;
+  if (s.spec_width > 0) {
+    spec = s.spec_width;
+  } else if (s.n_steps > 1) {
+    const int64_t fit = 65536 / (s.n_chains * (int64_t)L);
+    spec = (int)(fit < 1 ? 1 : (fit > smax ? smax : fit));
   }
-  set_error("two-scale Lorenz-96: no kernel compiled for J=%d (1, 2, 4, 8, 10, 16)", m.fast_per_slow);
-  return IPMC_ERR_UNSUPPORTED;
+  return IPMC_OK;
 }
 
-template <typename T, bool FM, int SPL>
-static int ts_eval_t(const ipmc_model& m, int64_t n, const void* u, const void* y, const void* ginv, void* out,
-                     bool phi, hipStream_t st) {
-  const int64_t blocks = ts_blocks(m.dim / SPL, n);
-  switch (m.fast_per_slow) {
-#define IPMC_J(J)                                                                                                 \
-  case J:                                                                                                         \
-    if constexpr (ts_compiled<SPL, J>()) {                                    \
-      if (phi)                                                                                                    \
-        hipLaunchKernelGGL((l96ts_eval_kernel<T, J, FM, SPL, true>), dim3((unsigned)blocks), dim3(kTsBlock), 0,   \
-                           st, m, n, (const T*)u, (const T*)y, (const T*)ginv, (T*)out);                          \
-      else                                                                                                        \
-        hipLaunchKernelGGL((l96ts_eval_kernel<T, J, FM, SPL, false>), dim3((unsigned)blocks), dim3(kTsBlock), 0,  \
-                           st, m, n, (const T*)u, (const T*)y, (const T*)ginv, (T*)out);                          \
-      return check_launch("l96ts_eval_kernel");                                                                   \
-    }                                                                                                             \
-    break;
-    IPMC_TS_J(IPMC_J)
-#undef IPMC_J
-  }
-  set_error("two-scale Lorenz-96: no kernel compiled for J=%d (1, 2, 4, 8, 10, 16)", m.fast_per_slow);
-  return IPMC_ERR_UNSUPPORTED;
-}
-
-int l96ts_sweep(const ipmc_model& m, const ipmc_sweep& s, hipStream_t st) {
+// The checks every entry point makes, and the slow variables per lane (s:
+// the sweep's request, nullptr for an evaluation).
+static int ts_layout(const ipmc_model& m, const ipmc_sweep* s, int* spl) {
   if (m.dim > 64) {
     set_error("two-scale Lorenz-96: K <= 64");
     return IPMC_ERR_UNSUPPORTED;
   }
-  const int spl = ts_spl(m, &s);
-  if (spl < 0) {
+  *spl = ts_spl(m, s);
+  if (*spl < 0) {
     set_error("two-scale Lorenz-96: lanes_per_chain must be K, (K even, J <= 10) K/2 or (K = 6, J <= 4) 2 or 1");
-    return IPMC_ERR_UNSUPPORTED;
-  }
-  const bool fm = m.arith == IPMC_ARITH_FMA;
-#define IPMC_TS_SPL_SWEEP(P)                                                                                       \
-  if (spl == P) {                                                                                                  \
-    if (s.dtype == IPMC_F64) return fm ? ts_sweep_t<double, true, P>(m, s, st) : ts_sweep_t<double, false, P>(m, s, st); \
-    return fm ? ts_sweep_t<float, true, P>(m, s, st) : ts_sweep_t<float, false, P>(m, s, st);                       \
-  }
-  IPMC_TS_SPL_SWEEP(2)
-  IPMC_TS_SPL_SWEEP(3)
-  IPMC_TS_SPL_SWEEP(6)
-#undef IPMC_TS_SPL_SWEEP
-  if (s.dtype == IPMC_F64) return fm ? ts_sweep_t<double, true, 1>(m, s, st) : ts_sweep_t<double, false, 1>(m, s, st);
-  return fm ? ts_sweep_t<float, true, 1>(m, s, st) : ts_sweep_t<float, false, 1>(m, s, st);
-}
-
-int l96ts_plan(const ipmc_model& m, const ipmc_sweep& s, int& lanes, int& spec) {
-  if (m.dim > 64) {
-    set_error("two-scale Lorenz-96: K <= 64");
-    return IPMC_ERR_UNSUPPORTED;
-  }
-  const int spl = ts_spl(m, &s);
-  if (spl < 0) {
-    set_error("two-scale Lorenz-96: lanes_per_chain must be K, (K even, J <= 10) K/2 or (K = 6, J <= 4) 2 or 1");
-    return IPMC_ERR_UNSUPPORTED;
-  }
-  lanes = m.dim / spl;
-  spec = ts_spec(s, lanes);
-  if (spec < 1) {
-    set_error("two-scale Lorenz-96: spec_width * lanes per chain (%d) must be <= 64", lanes);
     return IPMC_ERR_UNSUPPORTED;
   }
   return IPMC_OK;
 }
 
+// f(spl) / f(J) with an integral_constant tag, over the compiled values
+template <typename F>
+static int with_spl(int spl, F&& f) {
+  if (spl == 2) return f(std::integral_constant<int, 2>{});
+  if (spl == 3) return f(std::integral_constant<int, 3>{});
+  if (spl == 6) return f(std::integral_constant<int, 6>{});
+  return f(std::integral_constant<int, 1>{});
+}
+
+template <int SPL, typename F>
+static int with_J(int J, F&& f) {
+  switch (J) {
+#define IPMC_J(J) \
+  case J:         \
+    if constexpr (ts_compiled<SPL, J>()) return f(std::integral_constant<int, J>{}); \
+    break;
+    IPMC_TS_J(IPMC_J)
+#undef IPMC_J
+  }
+  set_error("two-scale Lorenz-96: no kernel compiled for J=%d (1, 2, 4, 8, 10, 16)", J);
+  return IPMC_ERR_UNSUPPORTED;
+}
+
+int l96ts_sweep(const ipmc_model& m, const ipmc_sweep& s, hipStream_t st) {
+  int spl, S;
+  int rc = ts_layout(m, &s, &spl);
+  if (!rc) rc = ts_spec(s, m.dim / spl, S);
+  if (rc) return rc;
+  const int64_t blocks = ts_blocks(m.dim / spl * S, s.n_chains);
+  return with_dtype(s.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return with_bool(m.arith == IPMC_ARITH_FMA, [&](auto fm) {
+      return with_spl(spl, [&](auto p) {
+        return with_J<decltype(p)::value>(m.fast_per_slow, [&](auto j) {
+          hipLaunchKernelGGL((l96ts_sweep_kernel<T, decltype(j)::value, decltype(fm)::value, decltype(p)::value>),
+                             dim3((unsigned)blocks), dim3(kTsBlock), 0, st, m, s, S);
+          return check_launch("l96ts_sweep_kernel");
+        });
+      });
+    });
+  });
+}
+
+int l96ts_plan(const ipmc_model& m, const ipmc_sweep& s, int& lanes, int& spec) {
+  int spl;
+  const int rc = ts_layout(m, &s, &spl);
+  if (rc) return rc;
+  lanes = m.dim / spl;
+  return ts_spec(s, lanes, spec);
+}
+
 int l96ts_eval(const ipmc_model& m, int32_t dtype, int64_t n, const void* u, const void* y, const void* ginv,
                void* out, bool phi, hipStream_t st) {
-  if (m.dim > 64) {
-    set_error("two-scale Lorenz-96: K <= 64");
-    return IPMC_ERR_UNSUPPORTED;
-  }
-  const bool fm = m.arith == IPMC_ARITH_FMA;
-  const int spl = ts_spl(m, nullptr);
-#define IPMC_TS_SPL_EVAL(P)                                                                                        \
-  if (spl == P) {                                                                                                  \
-    if (dtype == IPMC_F64)                                                                                         \
-      return fm ? ts_eval_t<double, true, P>(m, n, u, y, ginv, out, phi, st)                                       \
-                : ts_eval_t<double, false, P>(m, n, u, y, ginv, out, phi, st);                                     \
-    return fm ? ts_eval_t<float, true, P>(m, n, u, y, ginv, out, phi, st)                                          \
-              : ts_eval_t<float, false, P>(m, n, u, y, ginv, out, phi, st);                                        \
-  }
-  IPMC_TS_SPL_EVAL(2)
-  IPMC_TS_SPL_EVAL(3)
-  IPMC_TS_SPL_EVAL(6)
-#undef IPMC_TS_SPL_EVAL
-  if (dtype == IPMC_F64)
-    return fm ? ts_eval_t<double, true, 1>(m, n, u, y, ginv, out, phi, st)
-              : ts_eval_t<double, false, 1>(m, n, u, y, ginv, out, phi, st);
-  return fm ? ts_eval_t<float, true, 1>(m, n, u, y, ginv, out, phi, st)
-            : ts_eval_t<float, false, 1>(m, n, u, y, ginv, out, phi, st);
+  int spl;
+  const int rc = ts_layout(m, nullptr, &spl);
+  if (rc) return rc;
+  const int64_t blocks = ts_blocks(m.dim / spl, n);
+  return with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return with_bool(m.arith == IPMC_ARITH_FMA, [&](auto fm) {
+      return with_bool(phi, [&](auto ph) {
+        return with_spl(spl, [&](auto p) {
+          return with_J<decltype(p)::value>(m.fast_per_slow, [&](auto j) {
+            hipLaunchKernelGGL((l96ts_eval_kernel<T, decltype(j)::value, decltype(fm)::value, decltype(p)::value,
+                                                  decltype(ph)::value>),
+                               dim3((unsigned)blocks), dim3(kTsBlock), 0, st, m, n, (const T*)u, (const T*)y,
+                               (const T*)ginv, (T*)out);
+            return check_launch("l96ts_eval_kernel");
+          });
+        });
+      });
+    });
+  });
 }
 
 }  // namespace ipmc

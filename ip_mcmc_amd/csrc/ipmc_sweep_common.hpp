@@ -339,6 +339,24 @@ __device__ __forceinline__ void spec_path_replay(unsigned long long path, unsign
     visit(q++, la);
   }
 }
+// The in-wave decision of a chain on S slots of L lanes from lane `base` of
+// the wave (gmask: S*L low bits): one bit per slot, cast by its first lane.
+// The walk is resolved in parallel (spec_on_path): no cross-lane read inside
+// a data-dependent loop.  Every lane of the chain runs this.
+struct SpecWaveRound {
+  unsigned long long accm, path;  // bit n = node n: accepted, on the realised path
+  SpecRound rd;
+};
+__device__ __forceinline__ SpecWaveRound spec_wave_round(bool acc, bool ok, bool first, int base,
+                                                         unsigned long long gmask, int S, int L, int tb, int slot,
+                                                         bool act) {
+  SpecWaveRound w;
+  w.accm = spec_slot_bits((__ballot(acc && first) >> base) & gmask, S, L);
+  const unsigned long long okm = spec_slot_bits((__ballot(ok && first) >> base) & gmask, S, L);
+  w.path = spec_slot_bits((__ballot(spec_on_path(tb, slot, w.accm, act) && first) >> base) & gmask, S, L);
+  w.rd = spec_path_round(w.path, w.accm, okm);
+  return w;
+}
 
 // Node n's step from the slots' decision bits (bit n*L of acc / ok, L lanes
 // per slot) and the tree table.

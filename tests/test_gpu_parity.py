@@ -87,9 +87,10 @@ def test_forward_and_potential_bit_exact(dev, orc, dtype):
 # ----------------------------------------------------------------- sweep
 def _sweep_device(op, U0, phi0, y, ginv, sq, beta, seed, step0, n_steps, dtype, dev, lanes=0, box=None,
                   sched=None, chain_offset=0, want_sums=False, cpl=0, proposal="pcn", reg_scale=None, spec=1,
-                  chol=None):
+                  chol=None, sample_every=0):
     """One ipmc_pcn_sweep launch.  spec=1 (default) runs the sequential kernels;
-    spec=0 lets the library choose a speculation width, >1 forces one."""
+    spec=0 lets the library choose a speculation width, >1 forces one.
+    sample_every > 0: in-launch samples, `samp` is (C, n_steps // every, k)."""
     from ip_mcmc_amd import _abi
     from ip_mcmc_amd._lib import call
 
@@ -128,6 +129,11 @@ def _sweep_device(op, U0, phi0, y, ginv, sq, beta, seed, step0, n_steps, dtype, 
     s.seed, s.step0, s.n_steps = seed, step0, n_steps
     samp = torch.zeros_like(U)
     s.sample_out, s.sample_stride = samp.data_ptr(), U.shape[1]
+    if sample_every > 0:
+        n_s, k = n_steps // sample_every, U.shape[1]
+        samp = torch.zeros((U.shape[0], n_s, k), dtype=U.dtype, device=dev)
+        s.sample_out, s.sample_every = samp.data_ptr(), sample_every
+        s.sample_stride, s.sample_step_stride = n_s * k, k
     sums = None
     if want_sums:
         sums = (torch.zeros(U.shape, dtype=torch.float64, device=dev),
@@ -923,6 +929,48 @@ def test_speculative_recorded_states_short_launches(dev, orc, dtype):
                     _assert_same(d, o, what)
                     assert np.array_equal(d["sum_u"], o["sum_u"]), what
                     assert np.array_equal(d["sum_u2"], o["sum_u2"]), what
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_speculative_in_launch_samples_several_chains_per_wave(dev, orc, dtype):
+    """In-launch samples (sample_every = 3 over 17 steps: five samples, then two
+    steps, so a round is cut by the launch's end after the last sample) of the
+    in-wave speculative rounds with several chains per wave: Burgers GS = 16 at
+    widths 2 and 4 (two chains, one chain per wave), two-scale K = 11 at width 2
+    (G = 22: two chains and 20 idle lanes) and K = 3 at width 4 (G = 12: five
+    chains).  Expected: the oracle run in six launches of 3, 3, 3, 3, 3 and 2
+    steps, the state after each of the first five being a sample."""
+    from ip_mcmc_amd import BurgersOperator, TwoScaleLorenz96Operator
+
+    n, every = 17, 3
+    rng = np.random.default_rng(31)
+    rng.normal(size=30)  # the K = 6 operator of the test above comes first there: the same x0 draws
+    ts = {}
+    for K, J, arith in ((3, 1, "reference"), (11, 2, "fma")):
+        ts[K] = TwoScaleLorenz96Operator(K=K, J=J, x0=rng.normal(size=K * (1 + J)), dt=0.004, n_steps=25, arith=arith)
+    cases = [(BurgersOperator(N=128, dt_mode="cfl", T=0.2, arith="reference"), (2, 4)), (ts[11], (2,)), (ts[3], (4,))]
+    for (op, widths), scale in [(c, sc) for c in cases for sc in (0.2, 3.0)]:
+        U0, phi0, y, ginv, sq = _problem(op, 19, dtype, orc, seed=3)
+        ginv = ginv * scale
+        phi0 = orc.potential(op, U0, y, ginv, _np(dtype)).astype(np.float64)
+        o = dict(u=U0, phi=phi0)
+        acc, calls, samples = np.zeros(19, dtype=np.int64), np.zeros(19, dtype=np.int64), []
+        for i, steps in enumerate((3, 3, 3, 3, 3, 2)):
+            o = _sweep_oracle(orc, op, o["u"].astype(np.float64), o["phi"].astype(np.float64), y, ginv, sq, 0.3, 8,
+                              2**32 - 3 + every * i, steps, dtype)
+            acc, calls = acc + o["acc"], calls + o["calls"]
+            if steps == every:
+                samples.append(o["u"].copy())
+        samples = np.stack(samples, axis=1)
+        assert 0 < acc.sum() < 19 * n, (type(op).__name__, scale, acc.sum())  # both decisions occur
+        for w in widths:
+            d = _sweep_device(op, U0, phi0, y, ginv, sq, 0.3, 8, 2**32 - 3, n, dtype, dev, spec=w,
+                              sample_every=every)
+            what = (type(op).__name__, op.k, scale, w)
+            assert d["samp"].shape == samples.shape, what
+            assert np.array_equal(d["samp"], samples), what
+            assert np.array_equal(d["u"], o["u"]) and np.array_equal(d["phi"], o["phi"]), what
+            assert np.array_equal(d["acc"], acc) and np.array_equal(d["calls"], calls), what
 
 
 # ------------------------------------------------ non-diagonal priors (L·ξ)
