@@ -89,6 +89,16 @@ class ConstrainAccepter(AccepterBase):
         return False
 
 
+def _unwrap_accepter(accepter):
+    """(layers, core): a composition's CountedAccepter / ConstrainAccepter layers,
+    outermost first, and whatever lies beneath them (its callers judge that)."""
+    layers = []
+    while isinstance(accepter, (CountedAccepter, ConstrainAccepter)):
+        layers.append(accepter)
+        accepter = accepter.accepter
+    return layers, accepter
+
+
 class ProbabilisticAccepter(AccepterBase):
     """accepter.py:58-66: accept iff a(u, v) > rng.random() (strict)."""
 

@@ -91,6 +91,11 @@ class GaussianDistribution(DistributionBase):
             raise ValueError("sqrt_diagonal needs a diagonal covariance")
         return np.sqrt(np.diag(self.covariance))
 
+    def sqrt_factors(self):
+        """(sqrt_diagonal, None) for a diagonal C, else (None, L): w ~ N(0, C) is
+        sqrt(C_ii)·ξ_i, or L·ξ with L the lower Cholesky factor (ipmc_sweep.prior_chol)."""
+        return (self.sqrt_diagonal, None) if self.is_diagonal else (None, self.L)
+
     def log_normaliser(self):
         """½ (k log 2π + log det C): the constant in −logpdf that Φ drops."""
         return 0.5 * (self.k * np.log(2.0 * np.pi) + self._logdet)

@@ -34,12 +34,15 @@ Two tiers:
   ``random`` return the same counter-based draws (the reference's MockRNG seam,
   test_utilities.py:11-26).
 """
+import time
+
 import numpy as np
 import torch
 
 from . import device as dev
+from . import sampler as _shared  # the run bookkeeping of both tiers (names read at call time)
 from ._lib import call
-from .accepter import ConstrainAccepter, CountedAccepter, StandardRWAccepter, pCNAccepter
+from .accepter import CountedAccepter, StandardRWAccepter, _unwrap_accepter, pCNAccepter
 from .chainio import ChainState, NpySampleSink
 from .distribution import GaussianDistribution
 from .forward import ObservationOperator
@@ -50,17 +53,25 @@ DRAW_BLOCK_BYTES = 64 << 20
 
 
 # ------------------------------------------------------------------ draws
-def device_draws(seed, chain_offset, n_chains, step0, n_steps, k, np_dtype, prior_sqrt, prior_chol, device=None):
-    """(w [n_steps, C, k] in np_dtype, log r [n_steps, C] float64) from
-    ipmc_pcn_draws on `device`."""
+def _draws_on_device(seed, chain_offset, n_chains, step0, n_steps, k, np_dtype, prior_sqrt, prior_chol, device=None,
+                     log_r=True, shared_prior=False):
+    """ipmc_pcn_draws on `device`, left there: (w [n_steps, C, k] in np_dtype, log r [n_steps, C] float64
+    or None).  shared_prior: the prior factor's device copy is dev.const_to_device's, kept between calls."""
     device = dev.resolve_device(device)
     td = dev.torch_dtype(np_dtype)
-    sq = None if prior_sqrt is None else dev.to_device(prior_sqrt, td, device)
-    ch = None if prior_chol is None else dev.to_device(prior_chol, td, device)
+    to_device = dev.const_to_device if shared_prior else dev.to_device
+    sq = None if prior_sqrt is None else to_device(prior_sqrt, td, device)
+    ch = None if prior_chol is None else to_device(prior_chol, td, device)
     w = torch.empty((n_steps, n_chains, k), dtype=td, device=device)
-    lr = torch.empty((n_steps, n_chains), dtype=torch.float64, device=device)
+    lr = torch.empty((n_steps, n_chains), dtype=torch.float64, device=device) if log_r else None
     call("ipmc_pcn_draws", seed, chain_offset, n_chains, step0, n_steps, k, dev.abi_dtype(td), dev.ptr(sq),
-         dev.ptr(ch), w.data_ptr(), lr.data_ptr(), dev.stream_handle(device))
+         dev.ptr(ch), w.data_ptr(), dev.ptr(lr), dev.stream_handle(device))
+    return w, lr
+
+
+def device_draws(seed, chain_offset, n_chains, step0, n_steps, k, np_dtype, prior_sqrt, prior_chol, device=None):
+    """_draws_on_device's (w, log r), copied to the host as numpy arrays."""
+    w, lr = _draws_on_device(seed, chain_offset, n_chains, step0, n_steps, k, np_dtype, prior_sqrt, prior_chol, device)
     return w.cpu().numpy(), lr.cpu().numpy()
 
 
@@ -142,27 +153,13 @@ class HostPlan:
             raise ValueError(f"prior dimension {prior.k} != state dimension {k}")
         self.proposer = proposer
         self.rw = kind == "rw"
-        if prior.is_diagonal:
-            self.prior_sqrt, self.prior_chol = prior.sqrt_diagonal, None
-        else:
-            self.prior_sqrt, self.prior_chol = None, prior.L
-        self.layers = []  # ("count", CountedAccepter) | ("constrain", predicate), outermost first
-        acc = accepter
-        while True:
-            if isinstance(acc, CountedAccepter):
-                self.layers.append(("count", acc))
-                acc = acc.accepter
-            elif isinstance(acc, ConstrainAccepter):
-                self.layers.append(("constrain", acc.is_valid))
-                acc = acc.accepter
-            elif isinstance(acc, pCNAccepter):
-                self.reg_prior = None
-                break
-            elif isinstance(acc, StandardRWAccepter):
-                self.reg_prior = acc.prior
-                break
-            else:
-                raise GenericComposition(type(acc).__name__)
+        self.prior_sqrt, self.prior_chol = prior.sqrt_factors()
+        layers, acc = _unwrap_accepter(accepter)
+        # ("count", CountedAccepter) | ("constrain", predicate), outermost first
+        self.layers = [("count", a) if isinstance(a, CountedAccepter) else ("constrain", a.is_valid) for a in layers]
+        if not isinstance(acc, (pCNAccepter, StandardRWAccepter)):
+            raise GenericComposition(type(acc).__name__)
+        self.reg_prior = None if isinstance(acc, pCNAccepter) else acc.prior
         self.potential = acc.theta
         self.accept_kind = "pcn" if self.reg_prior is None else "rw_reg"
 
@@ -592,34 +589,23 @@ def run_generic(proposer, accepter, U, seed, chain_offset, step, n_burn, n_sampl
 
 
 # --------------------------------------------------------------------- run
-def run(sampler, u_0, n_samples, burn_in, sample_interval, keep, sample_file, reason):
-    """MCMCSampler.run for a composition outside the fused kernels' set."""
-    from .rng import PhiloxRNG, resolve_rng
-    from .sampler import _bump, _check_resume
+def _host_states(u_0, T):
+    """(U [C, k] as T, a copy; whether u_0 was one state); k is u_0's own, and 1 for a 0-d u_0."""
+    if isinstance(u_0, ChainState):
+        return np.array(u_0.u, dtype=T), False
+    if isinstance(u_0, torch.Tensor):
+        u_0 = u_0.detach().cpu().numpy()
+    arr = np.asarray(u_0, dtype=np.float64)
+    return np.atleast_2d(arr).astype(T).copy(), arr.ndim <= 1
 
-    if keep not in ("samples", "moments", "last"):
-        raise ValueError("keep must be 'samples', 'moments' or 'last'")
+
+def run(sampler, u_0, n_samples, n_burn, sample_interval, keep, sample_file, reason):
+    """MCMCSampler.run, after its checks, for a composition outside the fused kernels' set."""
+    rng = sampler.rng
     T = np.float64 if dev.torch_dtype(sampler.dtype) == dev.F64 else np.float32
     device = sampler.device  # resolved where a device call needs it (draws, a device G)
-    resume = isinstance(u_0, ChainState)
-    if resume:
-        single = False
-        U = np.array(u_0.u, dtype=T)
-    else:
-        if isinstance(u_0, torch.Tensor):
-            u_0 = u_0.detach().cpu().numpy()
-        arr = np.asarray(u_0, dtype=np.float64)
-        single = arr.ndim <= 1
-        U = np.atleast_2d(arr).astype(T).copy()
-        if arr.ndim == 0:
-            U = U.reshape(1, 1)
+    U, single = _host_states(u_0, T)
     n_chains, k = U.shape
-    n_samples, sample_interval = int(n_samples), int(sample_interval)
-    if n_samples < 0 or sample_interval < 0:
-        raise ValueError("n_samples and sample_interval must be >= 0")
-    if not isinstance(sampler.rng, PhiloxRNG):
-        sampler.rng = resolve_rng(sampler.rng)
-    rng = sampler.rng
     try:
         plan = HostPlan(sampler.proposer, sampler.accepter, k)
     except GenericComposition:
@@ -627,83 +613,48 @@ def run(sampler, u_0, n_samples, burn_in, sample_interval, keep, sample_file, re
     # a generic run caches no accept potential (its Φ is NaN): "generic" tells a
     # later structured or device run to recompute Φ(u) instead of reusing it
     accept_kind = "generic" if plan is None else plan.accept_kind
-    if resume:
-        _check_resume(u_0, sampler.chain_offset, accept_kind)
-        rng.seed, rng.step = u_0.seed, u_0.step
-        if hasattr(sampler.proposer, "i"):
-            sampler.proposer.i = u_0.proposer_i
-    if isinstance(sampler.accepter, CountedAccepter):
-        sampler.accepter.reset()  # sampler.py:15-16
-    n_burn = max(0, burn_in - sample_interval)  # sampler.py:18
+    state_dtype = "float64" if T == np.float64 else "float32"
+    reuse_phi = _shared._begin_run(sampler, u_0, accept_kind, state_dtype, n_chains)
     # interval 0 records the same state n_samples times (the reference's loop does)
     eff_interval = sample_interval if sample_interval > 0 else 1
     rec = _Recorder(keep, n_chains, n_samples, k, single, sample_file)
-    state_dtype = "float64" if T == np.float64 else "float32"
     prop_i = getattr(sampler.proposer, "i", 0)
-    import time
-
     t0 = time.perf_counter()
     calls_np = None
     # sample_interval 0: burn in, then every sample is the same state (the
     # reference's loop runs no step between its records, sampler.py:23-28)
     n_rec = n_samples if sample_interval > 0 else 0
+    where = (rng.seed, sampler.chain_offset, rng.step)
     if plan is not None:
-        if (resume and u_0.dtype == state_dtype and u_0.phi.shape[0] == n_chains
-                and u_0.accept_kind != "generic"):
-            phi = np.array(u_0.phi, dtype=T)
-        else:
-            phi = initial_phi(plan, U, device)
-        acc_np, counts, total = run_structured(plan, U, phi, rng.seed, sampler.chain_offset, rng.step, prop_i,
-                                               n_burn, n_rec, eff_interval, rec, device, sampler.verbose)
-        ci = 0
-        inner = False
-        for kind, obj in plan.layers:
+        phi = np.array(u_0.phi, dtype=T) if reuse_phi else initial_phi(plan, U, device)
+        acc_np, counts, total = run_structured(plan, U, phi, *where, prop_i, n_burn, n_rec, eff_interval, rec, device,
+                                               sampler.verbose)
+        inner, counts = False, iter(counts)
+        for kind, obj in plan.layers:  # ChainState.calls: the first CountedAccepter inside a ConstrainAccepter
             if kind == "count":
-                c = counts[ci]
-                ci += 1
-                _bump(obj, c, acc_np, single)
+                c = next(counts)
+                _shared._bump(obj, c, acc_np, single)
                 if inner and calls_np is None:
                     calls_np = c
             else:
                 inner = True
     else:
         phi = np.full(n_chains, np.nan, dtype=T)
-        counted = _counted(sampler.accepter)
-        prev = [(ca.calls, ca.accepts) for ca in counted]
-        counted, per, total, acc_np = run_generic(sampler.proposer, sampler.accepter, U, rng.seed,
-                                                  sampler.chain_offset, rng.step, n_burn, n_rec, eff_interval, rec,
-                                                  device, sampler.verbose)
+        prev = [(ca.calls, ca.accepts) for ca in _counted(sampler.accepter)]
+        counted, per, total, acc_np = run_generic(sampler.proposer, sampler.accepter, U, *where, n_burn, n_rec,
+                                                  eff_interval, rec, device, sampler.verbose)
         for ca, (c0, a0) in zip(counted, prev):
             # per-chain arrays for many chains, ints for one (the device path's convention)
             c, a = per[id(ca)]
             ca.calls, ca.accepts = c0, a0
-            _bump(ca, c, a, single)
+            _shared._bump(ca, c, a, single)
     if sample_interval == 0:
         for i in range(n_samples):
             rec.record(i, U)
     sampler.last_run_seconds = time.perf_counter() - t0
     sampler.last_path = "host" if plan is not None else "host-generic"
     sampler.last_host_reason = reason
-    rng.step += total
-    prop_i += total
-    if hasattr(sampler.proposer, "i"):
-        sampler.proposer.i = prop_i
-    if sampler.verbose and isinstance(sampler.accepter, CountedAccepter):
-        print(f"Acceptance ratio: {sampler.accepter.ratio()}")  # sampler.py:30-31
-    prev_acc = u_0.accepts if resume else 0
-    prev_calls = u_0.calls if (resume and u_0.calls is not None) else 0
-    sampler.state = ChainState(U.copy(), np.asarray(phi).copy(), prev_acc + acc_np,
-                               None if calls_np is None else prev_calls + calls_np, rng.seed, rng.step, prop_i,
-                               state_dtype, chain_offset=sampler.chain_offset, accept_kind=accept_kind)
-    sampler.state.steps_this_run = total
-    if keep == "samples":
-        if rec.sink is not None:
-            return rec.sink.close()
-        return rec.samples[0] if single else rec.samples
-    if keep == "moments":
-        n_post = n_samples * sample_interval
-        if single:
-            return {"sum_u": rec.sum_u[0], "sum_u2": rec.sum_u2[0], "n": n_post}
-        return {"sum_u": rec.sum_u, "sum_u2": rec.sum_u2, "n": n_post}
-    last = U.astype(np.float64)
-    return last[0] if single else last
+    _shared._finish_run(sampler, u_0, total, prop_i + total, U.copy(), np.asarray(phi).copy(), acc_np, calls_np,
+                        accept_kind, state_dtype)
+    value = rec.samples if keep == "samples" else (rec.sum_u, rec.sum_u2) if keep == "moments" else U.astype(np.float64)
+    return _shared._shape_result(keep, single, value, n_samples * sample_interval, rec.sink)

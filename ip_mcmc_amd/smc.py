@@ -38,7 +38,7 @@ import torch
 from . import _abi
 from . import device as dev
 from ._lib import UnsupportedOnDevice, call
-from .accepter import ConstrainAccepter, CountedAccepter, StandardRWAccepter, pCNAccepter
+from .accepter import ConstrainAccepter, CountedAccepter, StandardRWAccepter, _unwrap_accepter, pCNAccepter
 from .diagnostics import _on_device
 from .distribution import GaussianDistribution
 from .potential import EvolutionPotential
@@ -328,17 +328,15 @@ class SMCResult:
 def _unwrap_potential(potential):
     acc = potential
     while True:
-        if isinstance(acc, ConstrainAccepter):
+        layers, acc = _unwrap_accepter(acc)
+        if any(isinstance(lay, ConstrainAccepter) for lay in layers):
             raise NotImplementedError("TemperedSMC: ConstrainAccepter is not supported (a truncated prior needs "
                                       "rejection at the prior draw)")
         if isinstance(acc, StandardRWAccepter):
             raise NotImplementedError("TemperedSMC: random-walk accepters are not supported (the mutation is pCN)")
-        if isinstance(acc, CountedAccepter):
-            acc = acc.accepter
-        elif isinstance(acc, pCNAccepter):
-            acc = acc.theta
-        else:
+        if not isinstance(acc, pCNAccepter):
             break
+        acc = acc.theta
     if not isinstance(acc, EvolutionPotential):
         raise TypeError(f"TemperedSMC: potential must be an EvolutionPotential, not {type(acc).__name__}")
     if not isinstance(acc.rho, GaussianDistribution):
@@ -393,22 +391,16 @@ class TemperedSMC:
                                   GaussianDistribution(rho.mean, rho.covariance / t))
 
     def _prior_draw(self, n, tier, rng):
-        k = self.prior.k
-        sq, chol = (self.prior.sqrt_diagonal, None) if self.prior.is_diagonal else (None, self.prior.L)
-        if tier == "host":
-            from . import hostloop
+        from . import hostloop
 
+        block = (rng.seed, 0, n, rng.step, 1, self.prior.k)  # one step of n chains at the stream's position
+        if tier == "host":
             T = np.float64 if dev.torch_dtype(self.dtype) == dev.F64 else np.float32
-            w, _ = hostloop.DRAWS["w"](rng.seed, 0, n, rng.step, 1, k, T, sq, chol, self.device)
+            w, _ = hostloop.DRAWS["w"](*block, T, *self.prior.sqrt_factors(), self.device)
             return w[0].astype(np.float64)
-        device = dev.resolve_device(self.device)
-        td = dev.torch_dtype(self.dtype)
-        sq_t = None if sq is None else dev.const_to_device(sq, td, device)
-        ch_t = None if chol is None else dev.const_to_device(chol, td, device)
-        w = torch.empty((n, k), dtype=td, device=device)
-        call("ipmc_pcn_draws", rng.seed, 0, n, rng.step, 1, k, dev.abi_dtype(td), dev.ptr(sq_t), dev.ptr(ch_t),
-             w.data_ptr(), None, dev.stream_handle(device))
-        return w
+        w, _ = hostloop._draws_on_device(*block, self.dtype, *self.prior.sqrt_factors(), self.device, log_r=False,
+                                         shared_prior=True)
+        return w[0]
 
     def _phi1(self, u, tier):
         if tier == "device":
