@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <stdio.h>
 
+#include "ipmc_checks.hpp"
 #include "ipmc_internal.hpp"
 #include "ipmc_small.hpp"
 
@@ -12,38 +13,17 @@ namespace ipmc {
 
 static thread_local char g_err[512] = "";
 
-void set_error(const char* fmt, ...) {
+int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+  return code;
 }
 
 int check_launch(const char* what) {
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return IPMC_ERR_DEVICE;
-  }
-  return IPMC_OK;
-}
-
-static int fail(int code, const char* msg) {
-  set_error("%s", msg);
-  return code;
-}
-
-// The Philox counter holds the global chain id in one 32-bit word and the pCN
-// step in two (ipmc_device.hpp); host-side draws (rng.py) use steps from
-// kHostStepBase on.  Ids or steps outside these ranges would alias other
-// chains' draws, so they are rejected.
-constexpr int64_t kChainIdLimit = int64_t(1) << 32;
-constexpr uint64_t kHostStepBase = uint64_t(1) << 63;
-
-static int check_chain_range(int64_t chain_offset, int64_t n_chains) {
-  if (n_chains < 0 || chain_offset < 0) return fail(IPMC_ERR_INVALID, "negative count");
-  if (chain_offset > kChainIdLimit - n_chains)
-    return fail(IPMC_ERR_INVALID, "global chain ids (chain_offset + n_chains) must be <= 2^32");
+  if (e != hipSuccess) return fail(IPMC_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
   return IPMC_OK;
 }
 
@@ -162,10 +142,9 @@ static int l96_plan(const ipmc_model& m, const ipmc_sweep& s, int& lpc, int& cpl
   l96_layout(m.dim, s.dtype, s.n_chains, lpc, cpl);
   if (s.chains_per_lane) cpl = s.chains_per_lane;
   if (s.lanes_per_chain) lpc = s.lanes_per_chain;
-  if (!lpc || !l96_has(m.dim, s.dtype, lpc, cpl)) {
-    set_error("Lorenz-96: no kernel compiled for dim=%d lanes_per_chain=%d chains_per_lane=%d", m.dim, lpc, cpl);
-    return IPMC_ERR_UNSUPPORTED;
-  }
+  if (!lpc || !l96_has(m.dim, s.dtype, lpc, cpl))
+    return fail(IPMC_ERR_UNSUPPORTED, "Lorenz-96: no kernel compiled for dim=%d lanes_per_chain=%d chains_per_lane=%d",
+                m.dim, lpc, cpl);
   // speculation (l96_spec_kernel): spec_width slots of lpc lanes per chain,
   // auto = the widest keeping the ensemble within one wave per SIMD
   spec = s.spec_width;
@@ -298,11 +277,7 @@ template <typename T>
 __global__ void normal_kernel(uint64_t seed, int64_t c_off, int64_t n, uint64_t step, int k, T* out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * k) return;
-  const int64_t c = i / k;
-  const int j = (int)(i % k);
-  double z0, z1;
-  normal_pair(seed, (uint64_t)(c_off + c), step, (uint32_t)(j >> 1), z0, z1);
-  out[i] = (T)((j & 1) ? z1 : z0);
+  out[i] = normal_element<T>(i, seed, c_off, step, k);
 }
 
 // phi[c] = phi[c] + ½ Σ_j (c_j u_cj)²  (the sweep's I = Φ + regularizer, in its order)
@@ -322,15 +297,8 @@ __global__ void draws_kernel(uint64_t seed, int64_t c_off, int64_t n, uint64_t s
                              const T* __restrict__ sq, const T* __restrict__ chol, T* __restrict__ w,
                              double* __restrict__ log_r) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t sc = i / k;
-    const int j = (int)(i - sc * k);
-    const int64_t s = sc / n;
-    const uint64_t gid = (uint64_t)(c_off + (sc - s * n));
-    const uint64_t step = step0 + (uint64_t)s;
-    w[i] = draw_w<T>(seed, gid, step, j, k, sq, chol);
-    if (j == 0 && log_r) log_r[sc] = det_log(accept_uniform(seed, gid, step));
-  }
+       i += (int64_t)gridDim.x * blockDim.x)
+    draws_element<T>(i, seed, c_off, n, step0, k, sq, chol, w, log_r);
 }
 
 __global__ void uniform_kernel(uint64_t seed, int64_t c_off, int64_t n, uint64_t step, double* out) {
@@ -545,14 +513,9 @@ int ipmc_forward(const ipmc_model* m, int32_t dtype, int64_t n, const void* u, v
 
 int ipmc_normal(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t step, int32_t k, int32_t dtype,
                 void* out, void* stream) {
-  if (k < 0) return fail(IPMC_ERR_INVALID, "negative count");
-  const int rc = check_chain_range(chain_offset, n_chains);
-  if (rc) return rc;
-  if (dtype != IPMC_F32 && dtype != IPMC_F64) return fail(IPMC_ERR_INVALID, "bad dtype");
-  const int64_t total = n_chains * k;
-  if (total == 0) return IPMC_OK;
-  if (!out) return fail(IPMC_ERR_INVALID, "out is NULL");
-  const int64_t blocks = (total + 255) / 256;
+  const int rc = check_normal(chain_offset, n_chains, k, dtype, out);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
+  const int64_t blocks = (n_chains * k + 255) / 256;
   with_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     hipLaunchKernelGGL(normal_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, seed, chain_offset,
@@ -562,10 +525,8 @@ int ipmc_normal(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t 
 }
 
 int ipmc_uniform(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t step, double* out, void* stream) {
-  const int rc = check_chain_range(chain_offset, n_chains);
-  if (rc) return rc;
-  if (n_chains == 0) return IPMC_OK;
-  if (!out) return fail(IPMC_ERR_INVALID, "out is NULL");
+  const int rc = check_uniform(chain_offset, n_chains, out);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
   const int64_t blocks = (n_chains + 255) / 256;
   hipLaunchKernelGGL(uniform_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, seed, chain_offset,
                      n_chains, step, out);
@@ -575,17 +536,9 @@ int ipmc_uniform(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t
 int ipmc_pcn_draws(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t step0, int64_t n_steps,
                    int32_t k, int32_t dtype, const void* prior_sqrt, const void* prior_chol, void* w,
                    double* log_r, void* stream) {
-  if (k <= 0 || n_steps < 0) return fail(IPMC_ERR_INVALID, "k must be positive and n_steps >= 0");
-  int rc = check_chain_range(chain_offset, n_chains);
-  if (rc) return rc;
-  if (dtype != IPMC_F32 && dtype != IPMC_F64) return fail(IPMC_ERR_INVALID, "bad dtype");
-  if (step0 > kHostStepBase || (uint64_t)n_steps > kHostStepBase - step0)
-    return fail(IPMC_ERR_INVALID, "pCN steps must stay below 2^63 (the host-draw range)");
-  if (n_chains == 0 || n_steps == 0) return IPMC_OK;
-  if (!w) return fail(IPMC_ERR_INVALID, "w is NULL");
-  if (!prior_sqrt && !prior_chol) return fail(IPMC_ERR_INVALID, "prior_sqrt and prior_chol are both NULL");
-  if (n_chains > INT64_MAX / k / n_steps) return fail(IPMC_ERR_INVALID, "n_steps * n_chains * k overflows");
-  const int64_t total = n_steps * n_chains * k;
+  int64_t total;
+  const int rc = check_pcn_draws(chain_offset, n_chains, step0, n_steps, k, dtype, prior_sqrt, prior_chol, w, total);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
   const int64_t blocks = std::min<int64_t>((total + 255) / 256, 65536);
   with_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
@@ -603,10 +556,7 @@ int ipmc_copy_rows_d2h(void* dst, int64_t dst_pitch, const void* src, int64_t sr
   if (dst_pitch < width || src_pitch < width) return fail(IPMC_ERR_INVALID, "pitch < width");
   const hipError_t e = hipMemcpy2DAsync(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)width,
                                         (size_t)rows, hipMemcpyDeviceToHost, (hipStream_t)stream);
-  if (e != hipSuccess) {
-    set_error("hipMemcpy2DAsync: %s", hipGetErrorString(e));
-    return IPMC_ERR_DEVICE;
-  }
+  if (e != hipSuccess) return fail(IPMC_ERR_DEVICE, "hipMemcpy2DAsync: %s", hipGetErrorString(e));
   return IPMC_OK;
 }
 

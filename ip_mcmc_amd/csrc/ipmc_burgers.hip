@@ -686,10 +686,9 @@ static bool pick(int N, int64_t n_chains, int lanes, int& cpl, int& gs) {
 static int burgers_spec(const ipmc_sweep& s, int gs, int& spec) {
   if (s.spec_width > 0) {
     const int w = s.spec_width;
-    if ((w & (w - 1)) != 0 || (w * gs > 64 && w * gs != kBurBlock)) {
-      set_error("Burgers: spec_width must be a power of two with spec_width * %d lanes <= 64 or = 256", gs);
-      return IPMC_ERR_UNSUPPORTED;
-    }
+    if ((w & (w - 1)) != 0 || (w * gs > 64 && w * gs != kBurBlock))
+      return fail(IPMC_ERR_UNSUPPORTED,
+                  "Burgers: spec_width must be a power of two with spec_width * %d lanes <= 64 or = 256", gs);
     spec = w;
     return IPMC_OK;
   }
@@ -734,20 +733,17 @@ static int with_layout(int cpl, int gs, F&& f) {
 }
 
 static int validate(const ipmc_model& m, int64_t n_chains, int lanes, int& cpl, int& gs) {
-  if (m.q > kBurQMax) {
-    set_error("Burgers: at most %d observation windows", kBurQMax);
-    return IPMC_ERR_UNSUPPORTED;
-  }
+  if (m.q > kBurQMax) return fail(IPMC_ERR_UNSUPPORTED, "Burgers: at most %d observation windows", kBurQMax);
   if (!pick(m.dim, n_chains, lanes, cpl, gs) || (cpl != 4 && cpl != 8)) {
     // 8 cells per lane on up to 64 lanes, or 4 when N is no multiple of 8
     if (lanes > 0)
-      set_error("Burgers: N=%d lanes_per_chain=%d is not supported: N must be 4 or 8 cells on each of at most 64 lanes",
-                m.dim, lanes);
-    else
-      set_error("Burgers: N=%d is not supported: N must be a multiple of 8 and at most 512, or a multiple of 4 and at "
+      return fail(IPMC_ERR_UNSUPPORTED,
+                  "Burgers: N=%d lanes_per_chain=%d is not supported: N must be 4 or 8 cells on each of at most 64 lanes",
+                  m.dim, lanes);
+    return fail(IPMC_ERR_UNSUPPORTED,
+                "Burgers: N=%d is not supported: N must be a multiple of 8 and at most 512, or a multiple of 4 and at "
                 "most 256",
                 m.dim);
-    return IPMC_ERR_UNSUPPORTED;
   }
   return IPMC_OK;
 }

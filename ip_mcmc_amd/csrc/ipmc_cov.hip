@@ -289,45 +289,23 @@ extern "C" int ipmc_scatter(const void* x, int32_t dtype, int64_t n_chains, int6
                             int32_t center_mode, int64_t block_chains, double* scatter_out, double* dsum_out,
                             void* stream) {
   const char* fn = "ipmc_scatter";
-  if (n_chains < 0 || len < 0 || k < 0 || stride_chain < 0 || stride_t < 0 || stride_var < 0) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n_chains < 0 || len < 0 || k < 0 || stride_chain < 0 || stride_t < 0 || stride_var < 0)
+    return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n_chains == 0) return IPMC_OK;
-  if (k < 1 || k > 256) {
-    set_error("%s: k = %d outside [1, 256]", fn, k);
-    return IPMC_ERR_INVALID;
-  }
-  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
-    set_error("%s: bad dtype", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (center_mode != IPMC_CENTER_SHARED && center_mode != IPMC_CENTER_SPLIT) {
-    set_error("%s: bad center_mode %d", fn, center_mode);
-    return IPMC_ERR_INVALID;
-  }
-  if (block_chains < 1) {
-    set_error("%s: block_chains = %lld < 1", fn, (long long)block_chains);
-    return IPMC_ERR_INVALID;
-  }
-  if (!x || !center || !scatter_out) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (k < 1 || k > 256) return fail(IPMC_ERR_INVALID, "%s: k = %d outside [1, 256]", fn, k);
+  if (const int rc = check_dtype(fn, dtype)) return rc;
+  if (center_mode != IPMC_CENTER_SHARED && center_mode != IPMC_CENTER_SPLIT)
+    return fail(IPMC_ERR_INVALID, "%s: bad center_mode %d", fn, center_mode);
+  if (block_chains < 1) return fail(IPMC_ERR_INVALID, "%s: block_chains = %lld < 1", fn, (long long)block_chains);
+  if (!x || !center || !scatter_out) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   const bool split = center_mode == IPMC_CENTER_SPLIT;
-  if (len < (split ? 4 : 1)) {
-    set_error("%s: %lld samples per chain; %s", fn, (long long)len,
-              split ? "a split chain needs at least 2 (len >= 4)" : "the shared centre needs len >= 1");
-    return IPMC_ERR_INVALID;
-  }
-  if ((double)n_chains * (double)len * (double)k > 1e18) {
-    set_error("%s: more than 1e18 values in one call", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (2 * n_chains > 0x7fffffff) {
-    set_error("%s: at most %d chains per call", fn, 0x7fffffff / 2);
-    return IPMC_ERR_INVALID;
-  }
+  if (len < (split ? 4 : 1))
+    return fail(IPMC_ERR_INVALID, "%s: %lld samples per chain; %s", fn, (long long)len,
+                split ? "a split chain needs at least 2 (len >= 4)" : "the shared centre needs len >= 1");
+  if ((double)n_chains * (double)len * (double)k > 1e18)
+    return fail(IPMC_ERR_INVALID, "%s: more than 1e18 values in one call", fn);
+  if (2 * n_chains > 0x7fffffff)
+    return fail(IPMC_ERR_INVALID, "%s: at most %d chains per call", fn, 0x7fffffff / 2);
   if (block_chains > n_chains) block_chains = n_chains;  // one block: the same sums
   CovArgs a;
   a.n_chains = n_chains;
@@ -364,10 +342,7 @@ extern "C" int ipmc_scatter(const void* x, int32_t dtype, int64_t n_chains, int6
   const size_t lds = sizeof(double) * (size_t)doubles + (size_t)a.slab_rows * 2 * (sizeof(int64_t) + sizeof(int32_t));
   const int64_t nb = (n_chains + block_chains - 1) / block_chains;
   const int64_t groups = nb * (a.nt * (a.nt + 1) / 2);
-  if (groups > 0x7fffffff) {
-    set_error("%s: too many blocks for one call", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (groups > 0x7fffffff) return fail(IPMC_ERR_INVALID, "%s: too many blocks for one call", fn);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)groups), block((unsigned)threads);
   hipError_t attr = hipSuccess;
@@ -389,9 +364,6 @@ extern "C" int ipmc_scatter(const void* x, int32_t dtype, int64_t n_chains, int6
       });
     });
   });
-  if (attr != hipSuccess) {
-    set_error("%s: %s", fn, hipGetErrorString(attr));
-    return IPMC_ERR_DEVICE;
-  }
+  if (attr != hipSuccess) return fail(IPMC_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(attr));
   return check_launch("scatter_kernel");
 }

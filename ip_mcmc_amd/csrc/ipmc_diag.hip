@@ -612,31 +612,17 @@ __global__ __launch_bounds__(kDiagBlock) void moments_stats_kernel(const double*
 // -1 = nothing to do, else the status to return
 static int cv_check(const char* fn, const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k,
                     int64_t s_chain, int64_t s_t, int64_t s_var) {
-  if (n_chains < 0 || len < 0 || k < 0 || s_chain < 0 || s_t < 0 || s_var < 0) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n_chains < 0 || len < 0 || k < 0 || s_chain < 0 || s_t < 0 || s_var < 0)
+    return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n_chains == 0) return -1;
-  if (len < 4) {
-    set_error("%s: %lld samples per chain; a split chain needs at least 2 (len >= 4)", fn, (long long)len);
-    return IPMC_ERR_INVALID;
-  }
-  if (k < 1 || k > 256) {
-    set_error("%s: k = %d outside [1, 256]", fn, k);
-    return IPMC_ERR_INVALID;
-  }
-  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
-    set_error("%s: bad dtype", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (!x) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (2 * n_chains > 0x7fffffff / 256) {
-    set_error("%s: at most %d chains per call", fn, 0x7fffffff / 512);
-    return IPMC_ERR_INVALID;
-  }
+  if (len < 4)
+    return fail(IPMC_ERR_INVALID, "%s: %lld samples per chain; a split chain needs at least 2 (len >= 4)", fn,
+                (long long)len);
+  if (k < 1 || k > 256) return fail(IPMC_ERR_INVALID, "%s: k = %d outside [1, 256]", fn, k);
+  if (const int rc = check_dtype(fn, dtype)) return rc;
+  if (!x) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
+  if (2 * n_chains > 0x7fffffff / 256)
+    return fail(IPMC_ERR_INVALID, "%s: at most %d chains per call", fn, 0x7fffffff / 512);
   return 0;
 }
 
@@ -644,15 +630,10 @@ static int cv_check(const char* fn, const void* x, int32_t dtype, int64_t n_chai
 static int block_sums(const char* fn, const double* rows, int64_t n_rows, int64_t k, int64_t row_stride,
                       int64_t block_rows, double div, const double* center, bool centered, double* out,
                       void* stream) {
-  if (n_rows < 0 || k < 0 || row_stride < k || block_rows <= 0) {
-    set_error("%s: bad shape (n_rows, k >= 0, row_stride >= k, block_rows > 0)", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n_rows < 0 || k < 0 || row_stride < k || block_rows <= 0)
+    return fail(IPMC_ERR_INVALID, "%s: bad shape (n_rows, k >= 0, row_stride >= k, block_rows > 0)", fn);
   if (n_rows == 0 || k == 0) return IPMC_OK;
-  if (!rows || !out || (centered && !center)) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (!rows || !out || (centered && !center)) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   const int64_t lanes = (n_rows + block_rows - 1) / block_rows * k;
   // v / 1.0 == v: the term without the division gives the same bits sooner
   auto kern = centered ? block_sums_kernel<kBsCenteredSq>
@@ -668,28 +649,15 @@ using namespace ipmc;
 
 extern "C" int ipmc_autocorr(const void* x, int32_t dtype, int64_t n_series, int64_t len, int64_t stride_series,
                              int64_t stride_t, int32_t max_lag, double* out, void* stream) {
-  if (n_series < 0 || len < 0 || max_lag < 0) {
-    set_error("ipmc_autocorr: negative size");
-    return IPMC_ERR_INVALID;
-  }
+  if (n_series < 0 || len < 0 || max_lag < 0) return fail(IPMC_ERR_INVALID, "ipmc_autocorr: negative size");
   if (n_series == 0 || max_lag == 0) return IPMC_OK;
-  if (len == 0 || !x || !out) {
-    set_error("ipmc_autocorr: empty series or NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
-  if (max_lag > len) {
-    set_error("ipmc_autocorr: max_lag %d exceeds the series length %lld", max_lag, (long long)len);
-    return IPMC_ERR_INVALID;
-  }
+  if (len == 0 || !x || !out) return fail(IPMC_ERR_INVALID, "ipmc_autocorr: empty series or NULL pointer");
+  if (max_lag > len)
+    return fail(IPMC_ERR_INVALID, "ipmc_autocorr: max_lag %d exceeds the series length %lld", max_lag, (long long)len);
   const bool streamed = len > kAcMaxLen;
-  if (streamed && n_series > 0x7fffffff) {
-    set_error("ipmc_autocorr: at most 2^31 - 1 long series per call");
-    return IPMC_ERR_INVALID;
-  }
-  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
-    set_error("ipmc_autocorr: bad dtype");
-    return IPMC_ERR_INVALID;
-  }
+  if (streamed && n_series > 0x7fffffff)
+    return fail(IPMC_ERR_INVALID, "ipmc_autocorr: at most 2^31 - 1 long series per call");
+  if (const int rc = check_dtype("ipmc_autocorr", dtype)) return rc;
   const dim3 grid((unsigned)n_series, streamed ? (unsigned)((max_lag + kDiagBlock - 1) / kDiagBlock) : 1u);
   with_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
@@ -703,29 +671,19 @@ extern "C" int ipmc_autocorr(const void* x, int32_t dtype, int64_t n_series, int
 extern "C" int ipmc_burn_in(const void* x, int32_t dtype, int64_t n_chains, int32_t n_vars, int64_t len,
                             int64_t stride_chain, int64_t stride_var, int64_t stride_t, int32_t window,
                             double threshold, uint32_t* flags_scratch, int64_t* out, void* stream) {
-  if (n_chains < 0 || n_vars <= 0 || len < 0 || window <= 0) {
-    set_error("ipmc_burn_in: bad sizes (n_vars and window must be positive)");
-    return IPMC_ERR_INVALID;
-  }
+  if (n_chains < 0 || n_vars <= 0 || len < 0 || window <= 0)
+    return fail(IPMC_ERR_INVALID, "ipmc_burn_in: bad sizes (n_vars and window must be positive)");
   if (n_chains == 0) return IPMC_OK;
-  if (len < window) {
-    set_error("ipmc_burn_in: series of %lld samples shorter than the window %d", (long long)len, window);
-    return IPMC_ERR_INVALID;
-  }
-  if (!x || !out || !flags_scratch) {
-    set_error("ipmc_burn_in: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
-  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
-    set_error("ipmc_burn_in: bad dtype");
-    return IPMC_ERR_INVALID;
-  }
+  if (len < window)
+    return fail(IPMC_ERR_INVALID, "ipmc_burn_in: series of %lld samples shorter than the window %d", (long long)len,
+                window);
+  if (!x || !out || !flags_scratch) return fail(IPMC_ERR_INVALID, "ipmc_burn_in: NULL pointer");
+  int rc = check_dtype("ipmc_burn_in", dtype);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t words = (len + 31) / 32;
-  if (hipMemsetAsync(flags_scratch, 0, (size_t)(n_chains * words) * sizeof(uint32_t), st) != hipSuccess) {
-    set_error("ipmc_burn_in: memset failed");
-    return IPMC_ERR_DEVICE;
-  }
+  if (hipMemsetAsync(flags_scratch, 0, (size_t)(n_chains * words) * sizeof(uint32_t), st) != hipSuccess)
+    return fail(IPMC_ERR_DEVICE, "ipmc_burn_in: memset failed");
   const int64_t ns = n_chains * n_vars;
   const unsigned nb = (unsigned)((ns + 255) / 256);
   with_dtype(dtype, [&](auto tag) {
@@ -733,8 +691,7 @@ extern "C" int ipmc_burn_in(const void* x, int32_t dtype, int64_t n_chains, int3
     hipLaunchKernelGGL(burn_in_flags_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)x, n_chains, n_vars, len,
                        stride_chain, stride_var, stride_t, window, threshold, (unsigned*)flags_scratch, words);
   });
-  int rc = check_launch("burn_in_flags_kernel");
-  if (rc) return rc;
+  if ((rc = check_launch("burn_in_flags_kernel"))) return rc;
   hipLaunchKernelGGL(burn_in_search_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, st, n_chains, len,
                      window, (const unsigned*)flags_scratch, words, out);
   return check_launch("burn_in_search_kernel");
@@ -742,15 +699,10 @@ extern "C" int ipmc_burn_in(const void* x, int32_t dtype, int64_t n_chains, int3
 
 extern "C" int ipmc_ordered_sum(const double* rows, int64_t n_rows, int64_t k, int64_t row_stride, double div,
                                 double* acc, void* stream) {
-  if (n_rows < 0 || k < 0 || row_stride < k) {
-    set_error("ipmc_ordered_sum: bad shape (n_rows, k >= 0, row_stride >= k)");
-    return IPMC_ERR_INVALID;
-  }
+  if (n_rows < 0 || k < 0 || row_stride < k)
+    return fail(IPMC_ERR_INVALID, "ipmc_ordered_sum: bad shape (n_rows, k >= 0, row_stride >= k)");
   if (n_rows == 0 || k == 0) return IPMC_OK;
-  if (!rows || !acc) {
-    set_error("ipmc_ordered_sum: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
+  if (!rows || !acc) return fail(IPMC_ERR_INVALID, "ipmc_ordered_sum: NULL pointer");
   hipLaunchKernelGGL(ordered_sum_kernel, dim3((unsigned)((k + kOsCols - 1) / kOsCols)), dim3(kOsBlock), 0,
                      (hipStream_t)stream, rows, n_rows, k, row_stride, div, acc);
   return check_launch("ordered_sum_kernel");
@@ -772,10 +724,7 @@ extern "C" int ipmc_split_stats(const void* x, int32_t dtype, int64_t n_chains, 
                                 double* var_out, void* stream) {
   int rc = cv_check("ipmc_split_stats", x, dtype, n_chains, len, k, stride_chain, stride_t, stride_var);
   if (rc) return rc < 0 ? IPMC_OK : rc;
-  if (!mean_out || !var_out) {
-    set_error("ipmc_split_stats: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
+  if (!mean_out || !var_out) return fail(IPMC_ERR_INVALID, "ipmc_split_stats: NULL pointer");
   const int64_t N = len / 2, series = 2 * n_chains * k;
   const bool over_time = cv_lanes_over_time(N, k, stride_t);
   const int64_t per_block = over_time ? kDiagBlock / 64 : kDiagBlock;
@@ -792,31 +741,18 @@ extern "C" int ipmc_split_stats(const void* x, int32_t dtype, int64_t n_chains, 
 extern "C" int ipmc_mean_acov(const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k,
                               int64_t stride_chain, int64_t stride_t, int64_t stride_var, const double* mean,
                               int32_t max_lag, int64_t block_chains, double* partial_out, void* stream) {
-  if (max_lag < 0) {
-    set_error("ipmc_mean_acov: negative size");
-    return IPMC_ERR_INVALID;
-  }
+  if (max_lag < 0) return fail(IPMC_ERR_INVALID, "ipmc_mean_acov: negative size");
   int rc = cv_check("ipmc_mean_acov", x, dtype, n_chains, len, k, stride_chain, stride_t, stride_var);
   if (rc) return rc < 0 ? IPMC_OK : rc;
   const int64_t N = len / 2;
-  if (max_lag > N - 1) {
-    set_error("ipmc_mean_acov: max_lag %d exceeds len/2 - 1 = %lld", max_lag, (long long)(N - 1));
-    return IPMC_ERR_INVALID;
-  }
-  if (block_chains <= 0) {
-    set_error("ipmc_mean_acov: block_chains must be positive");
-    return IPMC_ERR_INVALID;
-  }
-  if (!mean || !partial_out) {
-    set_error("ipmc_mean_acov: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
+  if (max_lag > N - 1)
+    return fail(IPMC_ERR_INVALID, "ipmc_mean_acov: max_lag %d exceeds len/2 - 1 = %lld", max_lag, (long long)(N - 1));
+  if (block_chains <= 0) return fail(IPMC_ERR_INVALID, "ipmc_mean_acov: block_chains must be positive");
+  if (!mean || !partial_out) return fail(IPMC_ERR_INVALID, "ipmc_mean_acov: NULL pointer");
   const int64_t n_blocks = (2 * n_chains + block_chains - 1) / block_chains;
   const int64_t tiles = ((int64_t)max_lag + kDiagBlock) / kDiagBlock;  // ceil((max_lag + 1) / kDiagBlock)
-  if (tiles > 65535) {
-    set_error("ipmc_mean_acov: max_lag %d needs more than 65535 lag tiles", max_lag);
-    return IPMC_ERR_INVALID;
-  }
+  if (tiles > 65535)
+    return fail(IPMC_ERR_INVALID, "ipmc_mean_acov: max_lag %d needs more than 65535 lag tiles", max_lag);
   hipStream_t st = (hipStream_t)stream;
   const bool direct = N <= kCvDirectLen, streamed = N > kAcMaxLen;
   with_dtype(dtype, [&](auto tag) {
@@ -838,24 +774,14 @@ extern "C" int ipmc_mean_acov(const void* x, int32_t dtype, int64_t n_chains, in
 
 extern "C" int ipmc_moments_stats(const double* sum_u, const double* sum_u2, int64_t n_chains, int32_t k, int64_t n,
                                   double* mean_out, double* var_out, void* stream) {
-  if (n_chains < 0 || k < 0 || n < 0) {
-    set_error("ipmc_moments_stats: negative size");
-    return IPMC_ERR_INVALID;
-  }
+  if (n_chains < 0 || k < 0 || n < 0) return fail(IPMC_ERR_INVALID, "ipmc_moments_stats: negative size");
   if (n_chains == 0 || k == 0) return IPMC_OK;
-  if (n < 2) {
-    set_error("ipmc_moments_stats: a variance needs n >= 2 steps, got %lld", (long long)n);
-    return IPMC_ERR_INVALID;
-  }
-  if (!sum_u || !sum_u2 || !mean_out || !var_out) {
-    set_error("ipmc_moments_stats: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
+  if (n < 2)
+    return fail(IPMC_ERR_INVALID, "ipmc_moments_stats: a variance needs n >= 2 steps, got %lld", (long long)n);
+  if (!sum_u || !sum_u2 || !mean_out || !var_out) return fail(IPMC_ERR_INVALID, "ipmc_moments_stats: NULL pointer");
   const int64_t count = n_chains * k;
-  if ((count + kDiagBlock - 1) / kDiagBlock > 0x7fffffff) {
-    set_error("ipmc_moments_stats: too many values for one call");
-    return IPMC_ERR_INVALID;
-  }
+  if ((count + kDiagBlock - 1) / kDiagBlock > 0x7fffffff)
+    return fail(IPMC_ERR_INVALID, "ipmc_moments_stats: too many values for one call");
   hipLaunchKernelGGL(moments_stats_kernel, dim3((unsigned)((count + kDiagBlock - 1) / kDiagBlock)), dim3(kDiagBlock), 0,
                      (hipStream_t)stream, sum_u, sum_u2, count, (double)n, mean_out, var_out);
   return check_launch("moments_stats_kernel");

@@ -66,4 +66,27 @@ IPMC_HD double smc_weight(double phi, double phi_ref, double delta) {
   return det_exp(-(delta * (phi - phi_ref)));
 }
 
+// The ancestor of an offspring at position p of systematic resampling over the
+// cumulative weights cum[0 .. n), total = cum[n - 1] finite and > 0: the
+// smallest c with cum[c] > p, or, where p >= total by rounding, the first c
+// that holds the total (the last at which cum rises).  mid < n always.
+// libipmc_host.so calls it; ancestors_kernel (ipmc_smc.hip) keeps the same
+// search written out (profiles/r16), and test_ancestors_equal_the_host_twin
+// holds the two together.
+IPMC_HD int64_t smc_ancestor(double p, const double* cum, int64_t n, double total) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (cum[mid] > p) hi = mid; else lo = mid + 1;
+  }
+  if (lo == n) {
+    lo = 0, hi = n - 1;
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (cum[mid] >= total) hi = mid; else lo = mid + 1;
+    }
+  }
+  return lo;
+}
+
 }  // namespace ipmc

@@ -464,27 +464,14 @@ __global__ __launch_bounds__(kHsBlock) void histdd_kernel(const T* __restrict__ 
 // shared argument checks; 0 = go on, -1 = nothing to do, else the status to return
 int hs_check(const char* fn, const void* x, int32_t dtype, int64_t n_chains, int64_t len, int32_t k, int64_t s_chain,
              int64_t s_t, int64_t s_var) {
-  if (n_chains < 0 || len < 0 || k < 0 || s_chain < 0 || s_t < 0 || s_var < 0) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n_chains < 0 || len < 0 || k < 0 || s_chain < 0 || s_t < 0 || s_var < 0)
+    return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n_chains == 0) return -1;
-  if (k < 1 || k > 256) {
-    set_error("%s: k = %d outside [1, 256]", fn, k);
-    return IPMC_ERR_INVALID;
-  }
-  if (dtype != IPMC_F64 && dtype != IPMC_F32) {
-    set_error("%s: bad dtype", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (!x) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if ((double)n_chains * (double)(len > 0 ? len : 1) * (double)k > 1e18) {
-    set_error("%s: more than 1e18 values in one call", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (k < 1 || k > 256) return fail(IPMC_ERR_INVALID, "%s: k = %d outside [1, 256]", fn, k);
+  if (const int rc = check_dtype(fn, dtype)) return rc;
+  if (!x) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
+  if ((double)n_chains * (double)(len > 0 ? len : 1) * (double)k > 1e18)
+    return fail(IPMC_ERR_INVALID, "%s: more than 1e18 values in one call", fn);
   return 0;
 }
 
@@ -503,10 +490,7 @@ void hs_grid(int64_t total, int64_t* n_groups, int64_t* span) {
 
 int hs_zero(const char* fn, void* p, size_t bytes, hipStream_t st) {
   const hipError_t e = hipMemsetAsync(p, 0, bytes, st);
-  if (e != hipSuccess) {
-    set_error("%s: %s", fn, hipGetErrorString(e));
-    return IPMC_ERR_DEVICE;
-  }
+  if (e != hipSuccess) return fail(IPMC_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
   return IPMC_OK;
 }
 
@@ -520,10 +504,7 @@ extern "C" int ipmc_minmax(const void* x, int32_t dtype, int64_t n_chains, int64
                            double* max_out, double* scratch, void* stream) {
   int rc = hs_check("ipmc_minmax", x, dtype, n_chains, len, k, stride_chain, stride_t, stride_var);
   if (rc) return rc < 0 ? IPMC_OK : rc;
-  if (!min_out || !max_out || !scratch) {
-    set_error("ipmc_minmax: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
+  if (!min_out || !max_out || !scratch) return fail(IPMC_ERR_INVALID, "ipmc_minmax: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
   const HsGeom g = hs_geom(n_chains, len, k, stride_chain, stride_t, stride_var);
   double* pmin = scratch;
@@ -571,14 +552,8 @@ extern "C" int ipmc_hist1d(const void* x, int32_t dtype, int64_t n_chains, int64
                            const double* edges, int64_t* counts, int64_t* below, int64_t* above, void* stream) {
   int rc = hs_check("ipmc_hist1d", x, dtype, n_chains, len, k, stride_chain, stride_t, stride_var);
   if (rc) return rc < 0 ? IPMC_OK : rc;
-  if (bins < 1 || bins > 4096) {
-    set_error("ipmc_hist1d: bins = %d outside [1, 4096]", bins);
-    return IPMC_ERR_INVALID;
-  }
-  if (!edges || !counts || !below || !above) {
-    set_error("ipmc_hist1d: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
+  if (bins < 1 || bins > 4096) return fail(IPMC_ERR_INVALID, "ipmc_hist1d: bins = %d outside [1, 4096]", bins);
+  if (!edges || !counts || !below || !above) return fail(IPMC_ERR_INVALID, "ipmc_hist1d: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
   {
     const int64_t n = (int64_t)k * bins;  // >= k
@@ -603,10 +578,7 @@ extern "C" int ipmc_hist1d(const void* x, int32_t dtype, int64_t n_chains, int64
                      sizeof(uint32_t) * ((size_t)kt * (bins + 2) << copies_log2);
   int64_t n_groups, span;
   hs_grid(total, &n_groups, &span);
-  if (n_groups > 0x7fffffff) {
-    set_error("ipmc_hist1d: too many values for one call");
-    return IPMC_ERR_INVALID;
-  }
+  if (n_groups > 0x7fffffff) return fail(IPMC_ERR_INVALID, "ipmc_hist1d: too many values for one call");
   const dim3 grid((unsigned)n_groups, (unsigned)tiles), block(kHsBlock);
   with_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
@@ -625,14 +597,8 @@ extern "C" int ipmc_histdd(const void* x, int32_t dtype, int64_t n_chains, int64
                            void* stream) {
   int rc = hs_check("ipmc_histdd", x, dtype, n_chains, len, k, stride_chain, stride_t, stride_var);
   if (rc) return rc < 0 ? IPMC_OK : rc;
-  if (nd < 1 || nd > 4) {
-    set_error("ipmc_histdd: nd = %d outside [1, 4]", nd);
-    return IPMC_ERR_INVALID;
-  }
-  if (!comp || !bins || !edges || !counts) {
-    set_error("ipmc_histdd: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
+  if (nd < 1 || nd > 4) return fail(IPMC_ERR_INVALID, "ipmc_histdd: nd = %d outside [1, 4]", nd);
+  if (!comp || !bins || !edges || !counts) return fail(IPMC_ERR_INVALID, "ipmc_histdd: NULL pointer");
   HdAxes ax;
   ax.nd = nd;
   int64_t n_cells = 1;
@@ -640,24 +606,18 @@ extern "C" int ipmc_histdd(const void* x, int32_t dtype, int64_t n_chains, int64
   for (int d = 0; d < 4; ++d) {
     ax.bins[d] = 1, ax.eoff[d] = 0, ax.off[d] = 0;
     if (d >= nd) continue;
-    if (comp[d] < 0 || comp[d] >= k) {
-      set_error("ipmc_histdd: comp[%d] = %d outside [0, k = %d)", d, comp[d], k);
-      return IPMC_ERR_INVALID;
-    }
-    if (bins[d] < 1 || bins[d] > 4096) {
-      set_error("ipmc_histdd: bins = %d outside [1, 4096]", bins[d]);
-      return IPMC_ERR_INVALID;
-    }
+    if (comp[d] < 0 || comp[d] >= k)
+      return fail(IPMC_ERR_INVALID, "ipmc_histdd: comp[%d] = %d outside [0, k = %d)", d, comp[d], k);
+    if (bins[d] < 1 || bins[d] > 4096)
+      return fail(IPMC_ERR_INVALID, "ipmc_histdd: bins = %d outside [1, 4096]", bins[d]);
     ax.bins[d] = bins[d];
     ax.eoff[d] = n_edges;
     ax.off[d] = comp[d] * stride_var;
     n_edges += bins[d] + 1;
     n_cells *= bins[d];  // at most 2^48: no overflow before the check
   }
-  if (n_cells > ((int64_t)1 << 24)) {
-    set_error("ipmc_histdd: %lld cells exceed 2^24", (long long)n_cells);
-    return IPMC_ERR_INVALID;
-  }
+  if (n_cells > ((int64_t)1 << 24))
+    return fail(IPMC_ERR_INVALID, "ipmc_histdd: %lld cells exceed 2^24", (long long)n_cells);
   hipStream_t st = (hipStream_t)stream;
   if ((rc = hs_zero("ipmc_histdd", counts, sizeof(int64_t) * n_cells, st))) return rc;
   const int64_t total = n_chains * len;
@@ -671,10 +631,7 @@ extern "C" int ipmc_histdd(const void* x, int32_t dtype, int64_t n_chains, int64
   if (stride_chain == len * stride_t) g.inner_n = n_chains * len, g.n_chains = 1;
   int64_t n_groups, span;
   hs_grid(total, &n_groups, &span);
-  if (n_groups > 0x7fffffff) {
-    set_error("ipmc_histdd: too many values for one call");
-    return IPMC_ERR_INVALID;
-  }
+  if (n_groups > 0x7fffffff) return fail(IPMC_ERR_INVALID, "ipmc_histdd: too many values for one call");
   const bool in_lds = n_cells <= kDdLdsCells && n_edges <= kDdLdsEdges;
   const size_t lds = in_lds ? sizeof(double) * n_edges + sizeof(uint32_t) * n_cells : 0;
   const dim3 grid((unsigned)n_groups), block(kHsBlock);

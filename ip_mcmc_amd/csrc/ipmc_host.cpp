@@ -9,14 +9,13 @@
 
 #include "../../include/ipmc.h"
 #include "../../include/ipmc_host.h"
+#include "ipmc_checks.hpp"
 #include "ipmc_exp.hpp"
 #include "ipmc_rng.hpp"
 
-using namespace ipmc;
+namespace ipmc {
 
-namespace {
-
-thread_local char g_err[256] = "";
+static thread_local char g_err[256] = "";
 
 int fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -26,19 +25,14 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// the device library's ranges (ipmc_api.hip): 32-bit global chain ids, pCN
-// steps below 2^63 (host-side GaussianDistribution draws live above)
-constexpr int64_t kChainIdLimit = int64_t(1) << 32;
-constexpr uint64_t kHostStepBase = uint64_t(1) << 63;
+}  // namespace ipmc
+
+using namespace ipmc;
+
+namespace {
+
 // below this many elements one thread does the block (config 1's one chain)
 constexpr int64_t kParallelMin = int64_t(1) << 16;
-
-int check_chain_range(int64_t chain_offset, int64_t n_chains) {
-  if (n_chains < 0 || chain_offset < 0) return fail(IPMC_ERR_INVALID, "negative count");
-  if (chain_offset > kChainIdLimit - n_chains)
-    return fail(IPMC_ERR_INVALID, "global chain ids (chain_offset + n_chains) must be <= 2^32");
-  return IPMC_OK;
-}
 
 // fn(i0, i1) over [0, total) in contiguous slices, one per thread
 template <typename F>
@@ -59,20 +53,12 @@ void parallel_for(int64_t total, int n_threads, F fn) {
   for (auto& x : th) x.join();
 }
 
-// draws_kernel's element loop (ipmc_api.hip), element i = (s, c, j) row-major
+// draws_kernel's element loop (ipmc_api.hip)
 template <typename T>
 void draws(uint64_t seed, int64_t c_off, int64_t n, uint64_t step0, int64_t total, int k, const T* sq,
            const T* chol, T* w, double* log_r, int n_threads) {
   parallel_for(total, n_threads, [=](int64_t i0, int64_t i1) {
-    for (int64_t i = i0; i < i1; ++i) {
-      const int64_t sc = i / k;
-      const int j = (int)(i - sc * k);
-      const int64_t s = sc / n;
-      const uint64_t gid = (uint64_t)(c_off + (sc - s * n));
-      const uint64_t step = step0 + (uint64_t)s;
-      w[i] = draw_w<T>(seed, gid, step, j, k, sq, chol);
-      if (j == 0 && log_r) log_r[sc] = det_log(accept_uniform(seed, gid, step));
-    }
+    for (int64_t i = i0; i < i1; ++i) draws_element<T>(i, seed, c_off, n, step0, k, sq, chol, w, log_r);
   });
 }
 
@@ -129,17 +115,9 @@ const char* ipmc_host_last_error(void) { return g_err; }
 int ipmc_host_pcn_draws(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t step0, int64_t n_steps,
                         int32_t k, int32_t dtype, const void* prior_sqrt, const void* prior_chol, void* w,
                         double* log_r, int32_t n_threads) {
-  if (k <= 0 || n_steps < 0) return fail(IPMC_ERR_INVALID, "k must be positive and n_steps >= 0");
-  int rc = check_chain_range(chain_offset, n_chains);
-  if (rc) return rc;
-  if (dtype != IPMC_F32 && dtype != IPMC_F64) return fail(IPMC_ERR_INVALID, "bad dtype");
-  if (step0 > kHostStepBase || (uint64_t)n_steps > kHostStepBase - step0)
-    return fail(IPMC_ERR_INVALID, "pCN steps must stay below 2^63 (the host-draw range)");
-  if (n_chains == 0 || n_steps == 0) return IPMC_OK;
-  if (!w) return fail(IPMC_ERR_INVALID, "w is NULL");
-  if (!prior_sqrt && !prior_chol) return fail(IPMC_ERR_INVALID, "prior_sqrt and prior_chol are both NULL");
-  if (n_chains > INT64_MAX / k / n_steps) return fail(IPMC_ERR_INVALID, "n_steps * n_chains * k overflows");
-  const int64_t total = n_steps * n_chains * k;
+  int64_t total;
+  const int rc = check_pcn_draws(chain_offset, n_chains, step0, n_steps, k, dtype, prior_sqrt, prior_chol, w, total);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
   if (dtype == IPMC_F64)
     draws<double>(seed, chain_offset, n_chains, step0, total, k, (const double*)prior_sqrt,
                   (const double*)prior_chol, (double*)w, log_r, n_threads);
@@ -151,28 +129,21 @@ int ipmc_host_pcn_draws(uint64_t seed, int64_t chain_offset, int64_t n_chains, u
 
 int ipmc_host_normal(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t step, int32_t k,
                      int32_t dtype, void* out) {
-  if (k < 0) return fail(IPMC_ERR_INVALID, "negative count");
-  const int rc = check_chain_range(chain_offset, n_chains);
-  if (rc) return rc;
-  if (dtype != IPMC_F32 && dtype != IPMC_F64) return fail(IPMC_ERR_INVALID, "bad dtype");
+  const int rc = check_normal(chain_offset, n_chains, k, dtype, out);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
   const int64_t total = n_chains * k;
-  if (total == 0) return IPMC_OK;
-  if (!out) return fail(IPMC_ERR_INVALID, "out is NULL");
-  for (int64_t i = 0; i < total; ++i) {  // normal_kernel's element
-    const double z = normal_component(seed, (uint64_t)(chain_offset + i / k), step, (int)(i % k));
+  for (int64_t i = 0; i < total; ++i) {
     if (dtype == IPMC_F64)
-      ((double*)out)[i] = z;
+      ((double*)out)[i] = normal_element<double>(i, seed, chain_offset, step, k);
     else
-      ((float*)out)[i] = (float)z;
+      ((float*)out)[i] = normal_element<float>(i, seed, chain_offset, step, k);
   }
   return IPMC_OK;
 }
 
 int ipmc_host_uniform(uint64_t seed, int64_t chain_offset, int64_t n_chains, uint64_t step, double* out) {
-  const int rc = check_chain_range(chain_offset, n_chains);
-  if (rc) return rc;
-  if (n_chains == 0) return IPMC_OK;
-  if (!out) return fail(IPMC_ERR_INVALID, "out is NULL");
+  const int rc = check_uniform(chain_offset, n_chains, out);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
   for (int64_t c = 0; c < n_chains; ++c) out[c] = accept_uniform(seed, (uint64_t)(chain_offset + c), step);
   return IPMC_OK;
 }
@@ -214,16 +185,15 @@ int ipmc_host_ordered_sum(const double* rows, int64_t n_rows, int64_t k, int64_t
 
 int ipmc_host_temper_sums(const void* phi, int32_t dtype, int64_t n, double phi_ref, const double* deltas,
                           int32_t n_deltas, double* s1_out, double* s2_out) {
-  if (n < 0 || n_deltas < 0) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: negative size");
+  const char* fn = "ipmc_host_temper_sums";
+  if (n < 0 || n_deltas < 0) return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n == 0) return IPMC_OK;
-  if (n_deltas < 1 || n_deltas > IPMC_SMC_MAX_DELTAS)
-    return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: n_deltas = %d outside [1, %d]", n_deltas,
-                IPMC_SMC_MAX_DELTAS);
-  if (dtype != IPMC_F32 && dtype != IPMC_F64) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: bad dtype");
-  if (!phi || !deltas || !s1_out || !s2_out) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: NULL pointer");
+  int rc;
+  if ((rc = check_n_deltas(fn, n_deltas))) return rc;
+  if ((rc = check_dtype(fn, dtype))) return rc;
+  if (!phi || !deltas || !s1_out || !s2_out) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   for (int j = 0; j < n_deltas; ++j)
-    if (!(deltas[j] >= 0.0) || !(deltas[j] < __builtin_inf()))
-      return fail(IPMC_ERR_INVALID, "ipmc_host_temper_sums: deltas[%d] is not a finite number >= 0", j);
+    if ((rc = check_delta(fn, "deltas", j, deltas[j]))) return rc;
   if (dtype == IPMC_F64)
     temper_sums((const double*)phi, n, phi_ref, deltas, n_deltas, s1_out, s2_out);
   else
@@ -233,13 +203,13 @@ int ipmc_host_temper_sums(const void* phi, int32_t dtype, int64_t n, double phi_
 
 int ipmc_host_temper_cumweights(const void* phi, int32_t dtype, int64_t n, double phi_ref, double delta,
                                 double* cum_out) {
-  if (n < 0) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_cumweights: negative size");
+  const char* fn = "ipmc_host_temper_cumweights";
+  if (n < 0) return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n == 0) return IPMC_OK;
-  if (dtype != IPMC_F32 && dtype != IPMC_F64)
-    return fail(IPMC_ERR_INVALID, "ipmc_host_temper_cumweights: bad dtype");
-  if (!phi || !cum_out) return fail(IPMC_ERR_INVALID, "ipmc_host_temper_cumweights: NULL pointer");
-  if (!(delta >= 0.0) || !(delta < __builtin_inf()))
-    return fail(IPMC_ERR_INVALID, "ipmc_host_temper_cumweights: delta is not a finite number >= 0");
+  int rc;
+  if ((rc = check_dtype(fn, dtype))) return rc;
+  if (!phi || !cum_out) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
+  if ((rc = check_delta(fn, "delta", -1, delta))) return rc;
   if (dtype == IPMC_F64)
     temper_cumweights((const double*)phi, n, phi_ref, delta, cum_out);
   else
@@ -248,32 +218,15 @@ int ipmc_host_temper_cumweights(const void* phi, int32_t dtype, int64_t n, doubl
 }
 
 int ipmc_host_systematic_ancestors(const double* cum, int64_t n, double u, int64_t n_out, int64_t* anc_out) {
-  if (n < 0 || n_out < 0) return fail(IPMC_ERR_INVALID, "ipmc_host_systematic_ancestors: negative size");
-  if (!(u >= 0.0 && u < 1.0)) return fail(IPMC_ERR_INVALID, "ipmc_host_systematic_ancestors: u outside [0, 1)");
-  if (n == 0 || n_out == 0) return IPMC_OK;
-  if (!anc_out || !cum) return fail(IPMC_ERR_INVALID, "ipmc_host_systematic_ancestors: NULL pointer");
+  const int rc = check_ancestors("ipmc_host_systematic_ancestors", cum, n, u, n_out, anc_out);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
   const double total = cum[n - 1];
   if (!(total > 0.0) || !(total < __builtin_inf())) {
     for (int64_t i = 0; i < n_out; ++i) anc_out[i] = -1;
     return IPMC_OK;
   }
   const double step = total / (double)n_out;
-  for (int64_t i = 0; i < n_out; ++i) {
-    const double p = ((double)i + u) * step;
-    int64_t lo = 0, hi = n;  // the smallest c with cum[c] > p; n if there is none
-    while (lo < hi) {
-      const int64_t mid = lo + (hi - lo) / 2;
-      if (cum[mid] > p) hi = mid; else lo = mid + 1;
-    }
-    if (lo == n) {  // p >= total by rounding: the last c at which cum rises = the first that holds the total
-      lo = 0, hi = n - 1;
-      while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (cum[mid] >= total) hi = mid; else lo = mid + 1;
-      }
-    }
-    anc_out[i] = lo;
-  }
+  for (int64_t i = 0; i < n_out; ++i) anc_out[i] = smc_ancestor(((double)i + u) * step, cum, n, total);
   return IPMC_OK;
 }
 

@@ -6,13 +6,13 @@
 #include <type_traits>
 
 #include "../../include/ipmc.h"
+#include "ipmc_checks.hpp"  // fail (defined in ipmc_api.hip over ipmc_last_error()'s buffer), check_dtype
 
 namespace ipmc {
 
 // lanes of one Lorenz-96 speculative chain when its slots span a whole block
 constexpr int kL96SpecBlockLanes = 256;
 
-void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 
 // Run-time value -> template argument at a launch site.  f is a generic lambda:

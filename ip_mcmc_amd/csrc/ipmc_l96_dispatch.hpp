@@ -20,8 +20,8 @@ constexpr bool l96_ok() {
 
 // An (D, LPC) pair with no instantiation: report it through ipmc_last_error.
 inline int l96_unsupported(const ipmc_model& m, int lpc, const char* what) {
-  set_error("Lorenz-96: no %s kernel compiled for dim=%d lanes_per_chain=%d", what, m.dim, lpc);
-  return IPMC_ERR_UNSUPPORTED;
+  return fail(IPMC_ERR_UNSUPPORTED, "Lorenz-96: no %s kernel compiled for dim=%d lanes_per_chain=%d", what, m.dim,
+              lpc);
 }
 
 // spec > 1: the speculative kernel with spec slots of LPC lanes per chain.

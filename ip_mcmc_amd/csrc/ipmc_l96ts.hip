@@ -595,10 +595,8 @@ static int ts_spl(const ipmc_model& m, const ipmc_sweep* s) {
 // launches, the widest that keeps the ensemble within one wave per SIMD.
 static int ts_spec(const ipmc_sweep& s, int L, int& spec) {
   const int smax = 64 / L;
-  if (s.spec_width > smax) {
-    set_error("two-scale Lorenz-96: spec_width * lanes per chain (%d) must be <= 64", L);
-    return IPMC_ERR_UNSUPPORTED;
-  }
+  if (s.spec_width > smax)
+    return fail(IPMC_ERR_UNSUPPORTED, "two-scale Lorenz-96: spec_width * lanes per chain (%d) must be <= 64", L);
   spec = 1;
   if (s.spec_width > 0) {
     spec = s.spec_width;
@@ -612,15 +610,11 @@ static int ts_spec(const ipmc_sweep& s, int L, int& spec) {
 // The checks every entry point makes, and the slow variables per lane (s:
 // the sweep's request, nullptr for an evaluation).
 static int ts_layout(const ipmc_model& m, const ipmc_sweep* s, int* spl) {
-  if (m.dim > 64) {
-    set_error("two-scale Lorenz-96: K <= 64");
-    return IPMC_ERR_UNSUPPORTED;
-  }
+  if (m.dim > 64) return fail(IPMC_ERR_UNSUPPORTED, "two-scale Lorenz-96: K <= 64");
   *spl = ts_spl(m, s);
-  if (*spl < 0) {
-    set_error("two-scale Lorenz-96: lanes_per_chain must be K, (K even, J <= 10) K/2 or (K = 6, J <= 4) 2 or 1");
-    return IPMC_ERR_UNSUPPORTED;
-  }
+  if (*spl < 0)
+    return fail(IPMC_ERR_UNSUPPORTED,
+                "two-scale Lorenz-96: lanes_per_chain must be K, (K even, J <= 10) K/2 or (K = 6, J <= 4) 2 or 1");
   return IPMC_OK;
 }
 
@@ -643,8 +637,7 @@ static int with_J(int J, F&& f) {
     IPMC_TS_J(IPMC_J)
 #undef IPMC_J
   }
-  set_error("two-scale Lorenz-96: no kernel compiled for J=%d (1, 2, 4, 8, 10, 16)", J);
-  return IPMC_ERR_UNSUPPORTED;
+  return fail(IPMC_ERR_UNSUPPORTED, "two-scale Lorenz-96: no kernel compiled for J=%d (1, 2, 4, 8, 10, 16)", J);
 }
 
 int l96ts_sweep(const ipmc_model& m, const ipmc_sweep& s, hipStream_t st) {

@@ -440,31 +440,18 @@ SortLayout sort_layout(int64_t S, int k) {
 
 // shared argument checks; 0 = go on, -1 = nothing to do, else the status to return
 int rank_check(const char* fn, int64_t n_chains, int64_t len, int32_t k, bool negative_other) {
-  if (n_chains < 0 || len < 0 || k < 0 || negative_other) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n_chains < 0 || len < 0 || k < 0 || negative_other) return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n_chains == 0) return -1;
-  if (k < 1 || k > 256) {
-    set_error("%s: k = %d outside [1, 256]", fn, k);
-    return IPMC_ERR_INVALID;
-  }
+  if (k < 1 || k > 256) return fail(IPMC_ERR_INVALID, "%s: k = %d outside [1, 256]", fn, k);
   return 0;
 }
 
 int pooled_check(const char* fn, int64_t n_chains, int64_t len) {
-  if (len > 0 && n_chains > (kMaxPooled - 1) / len) {
-    set_error("%s: n_chains * len = %.0f pooled samples per component, the 32-bit permutation holds fewer than 2^32",
-              fn, (double)n_chains * (double)len);
-    return IPMC_ERR_INVALID;
-  }
+  if (len > 0 && n_chains > (kMaxPooled - 1) / len)
+    return fail(IPMC_ERR_INVALID,
+                "%s: n_chains * len = %.0f pooled samples per component, the 32-bit permutation holds fewer than 2^32",
+                fn, (double)n_chains * (double)len);
   return 0;
-}
-
-int bad_dtype(const char* fn, int32_t dtype) {
-  if (dtype == IPMC_F64 || dtype == IPMC_F32) return 0;
-  set_error("%s: bad dtype", fn);
-  return IPMC_ERR_INVALID;
 }
 
 }  // namespace
@@ -475,11 +462,8 @@ using namespace ipmc;
 extern "C" int ipmc_sort_workspace(int64_t n_chains, int64_t len, int32_t k, int32_t dtype, int64_t* bytes_out) {
   int rc = rank_check("ipmc_sort_workspace", n_chains, len, k, false);
   if (rc > 0) return rc;
-  if (rc == 0 && (rc = bad_dtype("ipmc_sort_workspace", dtype))) return rc;
-  if (!bytes_out) {
-    set_error("ipmc_sort_workspace: NULL pointer");
-    return IPMC_ERR_INVALID;
-  }
+  if (rc == 0 && (rc = check_dtype("ipmc_sort_workspace", dtype))) return rc;
+  if (!bytes_out) return fail(IPMC_ERR_INVALID, "ipmc_sort_workspace: NULL pointer");
   if (n_chains == 0) {
     *bytes_out = 0;
     return IPMC_OK;
@@ -496,19 +480,14 @@ extern "C" int ipmc_pooled_sort(const void* x, int32_t dtype, int64_t n_chains, 
   const char* fn = "ipmc_pooled_sort";
   int rc = rank_check(fn, n_chains, len, k, stride_chain < 0 || stride_t < 0 || stride_var < 0 || workspace_bytes < 0);
   if (rc) return rc < 0 ? IPMC_OK : rc;
-  if ((rc = bad_dtype(fn, dtype))) return rc;
-  if (!x || !sorted_out || !perm_out || !workspace) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if ((rc = check_dtype(fn, dtype))) return rc;
+  if (!x || !sorted_out || !perm_out || !workspace) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   if ((rc = pooled_check(fn, n_chains, len))) return rc;
   const int64_t S = n_chains * len;
   const SortLayout w = sort_layout(S, k);
-  if (workspace_bytes < w.bytes) {
-    set_error("%s: workspace of %lld bytes, ipmc_sort_workspace asks for %lld", fn, (long long)workspace_bytes,
-              (long long)w.bytes);
-    return IPMC_ERR_INVALID;
-  }
+  if (workspace_bytes < w.bytes)
+    return fail(IPMC_ERR_INVALID, "%s: workspace of %lld bytes, ipmc_sort_workspace asks for %lld", fn,
+                (long long)workspace_bytes, (long long)w.bytes);
   if (S == 0) return IPMC_OK;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
@@ -519,10 +498,7 @@ extern "C" int ipmc_pooled_sort(const void* x, int32_t dtype, int64_t n_chains, 
   unsigned long long* kdiff = (unsigned long long*)(ws + w.diff);
   uint8_t* plan = (uint8_t*)(ws + w.plan);
   const hipError_t e = hipMemsetAsync(kdiff, 0, sizeof(unsigned long long) * k, st);
-  if (e != hipSuccess) {
-    set_error("%s: %s", fn, hipGetErrorString(e));
-    return IPMC_ERR_DEVICE;
-  }
+  if (e != hipSuccess) return fail(IPMC_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
   const dim3 block(kSortBlock);
   {
     int64_t groups = (S + kKeyTile - 1) / kKeyTile;
@@ -568,14 +544,9 @@ extern "C" int ipmc_rank_scores(const double* sorted, const uint32_t* perm, int3
   int rc = rank_check(fn, n_chains, len, k,
                       out_stride_chain < 0 || out_stride_t < 0 || out_stride_var < 0 || workspace_bytes < 0);
   if (rc) return rc < 0 ? IPMC_OK : rc;
-  if (mode != 0 && mode != 1) {
-    set_error("%s: mode = %d is neither 0 (average rank) nor 1 (normal score)", fn, mode);
-    return IPMC_ERR_INVALID;
-  }
-  if (!sorted || !perm || !out) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (mode != 0 && mode != 1)
+    return fail(IPMC_ERR_INVALID, "%s: mode = %d is neither 0 (average rank) nor 1 (normal score)", fn, mode);
+  if (!sorted || !perm || !out) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   if ((rc = pooled_check(fn, n_chains, len))) return rc;
   const int64_t S = n_chains * len;
   if (S == 0) return IPMC_OK;

@@ -246,4 +246,26 @@ IPMC_HD T draw_w(uint64_t seed, uint64_t gid, uint64_t step, int j, int k, const
   return sq[j] * (T)((j & 1) ? z1 : z0);
 }
 
+// Element i = (s, c, j), row-major, of ipmc_pcn_draws / ipmc_host_pcn_draws
+// over n chains from global id c_off and steps from step0: w[i], and from the
+// j = 0 element log r of (s, c) where log_r is asked for.
+template <typename T>
+IPMC_HD void draws_element(int64_t i, uint64_t seed, int64_t c_off, int64_t n, uint64_t step0, int k, const T* sq,
+                           const T* chol, T* w, double* log_r) {
+  const int64_t sc = i / k;
+  const int j = (int)(i - sc * k);
+  const int64_t s = sc / n;
+  const uint64_t gid = (uint64_t)(c_off + (sc - s * n));
+  const uint64_t step = step0 + (uint64_t)s;
+  w[i] = draw_w<T>(seed, gid, step, j, k, sq, chol);
+  if (j == 0 && log_r) log_r[sc] = det_log(accept_uniform(seed, gid, step));
+}
+
+// Element i = (c, j), row-major, of ipmc_normal / ipmc_host_normal: ξ_j of
+// chain c_off + c at `step`, rounded to T.
+template <typename T>
+IPMC_HD T normal_element(int64_t i, uint64_t seed, int64_t c_off, uint64_t step, int k) {
+  return (T)normal_component(seed, (uint64_t)(c_off + i / k), step, (int)(i % k));
+}
+
 }  // namespace ipmc

@@ -22,6 +22,7 @@
 //                   share it, stores are dense, loads are dense inside a row.
 //
 // No workgroup waits on another; no atomics; nothing depends on the grid.
+#include "ipmc_checks.hpp"
 #include "ipmc_internal.hpp"
 #include "ipmc_exp.hpp"
 
@@ -166,6 +167,9 @@ __global__ __launch_bounds__(kSmcThreads) void ancestors_kernel(const double* __
       anc[i] = -1;
       continue;
     }
+    // Mirrors smc_ancestor (ipmc_exp.hpp), which only the host library calls: the search stays written out
+    // here, as at the parent commit, because the kernel that called smc_ancestor missed the timing criterion
+    // against the parent (profiles/r16/README.md, "Timing").  Keep the two in step.
     const double p = ((double)i + u) * step;
     int64_t lo = 0, hi = n;  // the smallest c with cum[c] > p; n if there is none.  mid < n always
     while (lo < hi) {
@@ -216,30 +220,11 @@ int64_t smc_blocks(int64_t n) { return (n + kSmcBlock - 1) / kSmcBlock; }
 
 int64_t smc_workspace_bytes(int64_t n, int32_t n_deltas) { return 2 * smc_blocks(n) * (int64_t)n_deltas * 8; }
 
-int smc_dtype(const char* fn, int32_t dtype) {
-  if (dtype == IPMC_F64 || dtype == IPMC_F32) return 0;
-  set_error("%s: bad dtype", fn);
-  return IPMC_ERR_INVALID;
-}
-
-int smc_delta(const char* fn, const char* name, int j, double delta) {
-  if (delta >= 0.0 && delta < __builtin_inf()) return 0;
-  if (j >= 0)
-    set_error("%s: %s[%d] is not a finite number >= 0", fn, name, j);
-  else
-    set_error("%s: %s is not a finite number >= 0", fn, name);
-  return IPMC_ERR_INVALID;
-}
-
 int smc_workspace_check(const char* fn, const void* workspace, int64_t have, int64_t need) {
-  if (!workspace) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (have < need) {
-    set_error("%s: workspace of %lld bytes, ipmc_smc_workspace asks for %lld", fn, (long long)have, (long long)need);
-    return IPMC_ERR_INVALID;
-  }
+  if (!workspace) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
+  if (have < need)
+    return fail(IPMC_ERR_INVALID, "%s: workspace of %lld bytes, ipmc_smc_workspace asks for %lld", fn, (long long)have,
+                (long long)need);
   return 0;
 }
 
@@ -252,18 +237,9 @@ using namespace ipmc;
 
 extern "C" int ipmc_smc_workspace(int64_t n, int32_t n_deltas, int64_t* bytes_out) {
   const char* fn = "ipmc_smc_workspace";
-  if (n < 0 || n_deltas < 0) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (n_deltas < 1 || n_deltas > kMaxDeltas) {
-    set_error("%s: n_deltas = %d outside [1, %d]", fn, n_deltas, kMaxDeltas);
-    return IPMC_ERR_INVALID;
-  }
-  if (!bytes_out) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n < 0 || n_deltas < 0) return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
+  if (const int rc = check_n_deltas(fn, n_deltas)) return rc;
+  if (!bytes_out) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   *bytes_out = smc_workspace_bytes(n, n_deltas);
   return IPMC_OK;
 }
@@ -272,25 +248,16 @@ extern "C" int ipmc_temper_sums(const void* phi, int32_t dtype, int64_t n, doubl
                                 int32_t n_deltas, double* s1_out, double* s2_out, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
   const char* fn = "ipmc_temper_sums";
-  if (n < 0 || n_deltas < 0 || workspace_bytes < 0) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n < 0 || n_deltas < 0 || workspace_bytes < 0) return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n == 0) return IPMC_OK;
-  if (n_deltas < 1 || n_deltas > kMaxDeltas) {
-    set_error("%s: n_deltas = %d outside [1, %d]", fn, n_deltas, kMaxDeltas);
-    return IPMC_ERR_INVALID;
-  }
   int rc;
-  if ((rc = smc_dtype(fn, dtype))) return rc;
-  if (!phi || !deltas || !s1_out || !s2_out) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if ((rc = check_n_deltas(fn, n_deltas))) return rc;
+  if ((rc = check_dtype(fn, dtype))) return rc;
+  if (!phi || !deltas || !s1_out || !s2_out) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   if ((rc = smc_workspace_check(fn, workspace, workspace_bytes, smc_workspace_bytes(n, n_deltas)))) return rc;
   Deltas dl = {};
   for (int j = 0; j < n_deltas; ++j) {
-    if ((rc = smc_delta(fn, "deltas", j, deltas[j]))) return rc;
+    if ((rc = check_delta(fn, "deltas", j, deltas[j]))) return rc;
     dl.d[j] = deltas[j];
   }
   const int64_t nb = smc_blocks(n);
@@ -311,19 +278,13 @@ extern "C" int ipmc_temper_sums(const void* phi, int32_t dtype, int64_t n, doubl
 extern "C" int ipmc_temper_cumweights(const void* phi, int32_t dtype, int64_t n, double phi_ref, double delta,
                                       double* cum_out, void* workspace, int64_t workspace_bytes, void* stream) {
   const char* fn = "ipmc_temper_cumweights";
-  if (n < 0 || workspace_bytes < 0) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n < 0 || workspace_bytes < 0) return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n == 0) return IPMC_OK;
   int rc;
-  if ((rc = smc_dtype(fn, dtype))) return rc;
-  if (!phi || !cum_out) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if ((rc = check_dtype(fn, dtype))) return rc;
+  if (!phi || !cum_out) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   if ((rc = smc_workspace_check(fn, workspace, workspace_bytes, smc_workspace_bytes(n, 1)))) return rc;
-  if ((rc = smc_delta(fn, "delta", -1, delta))) return rc;
+  if ((rc = check_delta(fn, "delta", -1, delta))) return rc;
   const int64_t nb = smc_blocks(n);
   double* totals = (double*)workspace;
   double* offsets = totals + nb;
@@ -344,20 +305,8 @@ extern "C" int ipmc_temper_cumweights(const void* phi, int32_t dtype, int64_t n,
 
 extern "C" int ipmc_systematic_ancestors(const double* cum, int64_t n, double u, int64_t n_out, int64_t* anc_out,
                                          void* stream) {
-  const char* fn = "ipmc_systematic_ancestors";
-  if (n < 0 || n_out < 0) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (!(u >= 0.0 && u < 1.0)) {
-    set_error("%s: u outside [0, 1)", fn);
-    return IPMC_ERR_INVALID;
-  }
-  if (n == 0 || n_out == 0) return IPMC_OK;
-  if (!cum || !anc_out) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  const int rc = check_ancestors("ipmc_systematic_ancestors", cum, n, u, n_out, anc_out);
+  if (rc) return rc < 0 ? IPMC_OK : rc;
   int64_t groups = (n_out + kSmcThreads - 1) / kSmcThreads;
   if (groups > 4096) groups = 4096;
   hipLaunchKernelGGL(ancestors_kernel, dim3((unsigned)groups), dim3(kSmcThreads), 0, (hipStream_t)stream, cum, n, u,
@@ -368,38 +317,20 @@ extern "C" int ipmc_systematic_ancestors(const double* cum, int64_t n, double u,
 extern "C" int ipmc_gather_rows(const void* src, int32_t dtype, int64_t n_src, int32_t k, int64_t src_stride,
                                 const int64_t* idx, int64_t n_out, void* dst, int64_t dst_stride, void* stream) {
   const char* fn = "ipmc_gather_rows";
-  if (n_src < 0 || n_out < 0 || k < 0 || src_stride < 0 || dst_stride < 0) {
-    set_error("%s: negative size", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n_src < 0 || n_out < 0 || k < 0 || src_stride < 0 || dst_stride < 0)
+    return fail(IPMC_ERR_INVALID, "%s: negative size", fn);
   if (n_out == 0) return IPMC_OK;
-  if (k < 1 || k > 256) {
-    set_error("%s: k = %d outside [1, 256]", fn, k);
-    return IPMC_ERR_INVALID;
-  }
-  if (src_stride < k || dst_stride < k) {
-    set_error("%s: a row stride is below k = %d", fn, k);
-    return IPMC_ERR_INVALID;
-  }
-  int rc;
-  if ((rc = smc_dtype(fn, dtype))) return rc;
-  if (!idx || !dst || (n_src > 0 && !src)) {
-    set_error("%s: NULL pointer", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (k < 1 || k > 256) return fail(IPMC_ERR_INVALID, "%s: k = %d outside [1, 256]", fn, k);
+  if (src_stride < k || dst_stride < k) return fail(IPMC_ERR_INVALID, "%s: a row stride is below k = %d", fn, k);
+  if (const int rc = check_dtype(fn, dtype)) return rc;
+  if (!idx || !dst || (n_src > 0 && !src)) return fail(IPMC_ERR_INVALID, "%s: NULL pointer", fn);
   const int64_t esize = dtype == IPMC_F64 ? 8 : 4;
   const int64_t max_rows = (INT64_MAX / esize - k) / (src_stride > dst_stride ? src_stride : dst_stride);
-  if (n_src > max_rows || n_out > max_rows) {
-    set_error("%s: rows * stride overflows", fn);
-    return IPMC_ERR_INVALID;
-  }
+  if (n_src > max_rows || n_out > max_rows) return fail(IPMC_ERR_INVALID, "%s: rows * stride overflows", fn);
   if (n_src > 0) {
     const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (uintptr_t)(((n_src - 1) * src_stride + k) * esize);
     const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)(((n_out - 1) * dst_stride + k) * esize);
-    if (s0 < d1 && d0 < s1) {
-      set_error("%s: dst overlaps src (the gather is out of place)", fn);
-      return IPMC_ERR_INVALID;
-    }
+    if (s0 < d1 && d0 < s1) return fail(IPMC_ERR_INVALID, "%s: dst overlaps src (the gather is out of place)", fn);
   }
   const int rows_per_tile = kGatherElems / k > 0 ? kGatherElems / k : 1;
   const int64_t n_tiles = (n_out + rows_per_tile - 1) / rows_per_tile;
